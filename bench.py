@@ -15,16 +15,20 @@ mirror is replicated.
 `value` = candidate placements (appendProbNode evaluations the reference's search issues, M:7011 / 7223, counted by the
 search itself) of all ranks in the K timed steps / wall time (max over ranks).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Prints ONE JSON line on rank 0.  Everything the searches read is resident in HBM before the timed region starts.
 
-Next to the headline the default run has (rank 0, N = 1): a second leg on BASELINE configs[3]'s tree (`config_1M`: 1 000 000
-samples, full model, 131 072 searches per step), a third on configs[4] (`config_5`: 50 000 samples added to that tree one after the
-other -- the serial placement loop with its samples announced, maple_placement_ahead -- then a round), a whole round on a
-changing tree at the headline's size (`changing_tree`: search, every proposed move re-searched and applied, the next round),
-`tree_log_lk` against the oracle and `cpu_baseline`; everything else goes to bench_detail.json.
+A plain run does what the headline needs and nothing else: it builds the tree, warms up, times the K steps and prints the
+line.  `--dump-outputs DIR` then writes what the last timed step returned (dump_outputs).  `--full` adds everything else the
+bench measures or checks (rank 0, N = 1): the step after the tree is uploaded again (`first_step_after_upload_ms`), the
+sub-blocks (sub_blocks, among them a whole round on a changing tree at the headline's size, `changing_tree`: search, every
+proposed move re-searched and applied, the next round), `tree_log_lk` against the oracle, `cpu_baseline`, a second leg on
+BASELINE configs[3]'s tree (`config_1M`: 1 000 000 samples, full model, 131 072 searches per step) and a third on configs[4]
+(`config_5`: 50 000 samples added to that tree one after the other -- the serial placement loop with its samples announced,
+maple_placement_ahead -- then a round); `--no-extras`, `--no-cpu-baseline` and `--no-1m` leave parts of it out.  Everything
+that does not fit the line goes to bench_detail.json.
 """
 import argparse
 import glob
@@ -159,6 +163,12 @@ def parse_args(argv=None):
                     help="generator of the synthetic input: v1 = maple_amd.synth.make_dataset (numpy stream; the 10 000 / 100 000-sample "
                          "trees of rounds 1-4: 21 s at 100 000 samples), v2 = the same model from csrc/synth_gen.c (1 s at 1 000 000 "
                          "samples); auto = v2")
+    ap.add_argument("--full", action="store_true",
+                    help="everything the bench measures or checks next to the headline: the step after a re-upload of the tree, the "
+                         "sub-blocks, tree_log_lk, cpu_baseline and the configs[3] / configs[4] legs (off: the headline alone)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (rank 0) as DIR/<name>.npy in float64 "
+                         "(at most 64 MB: a fixed, seeded sample of the rows of a larger output)")
     ap.add_argument("--queries", type=int, default=256, help="query lists of the all-pairs scoring sub-block")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="approximate host time spent on cpu_baseline")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -166,13 +176,16 @@ def parse_args(argv=None):
     ap.add_argument("--local-refs", action="store_true",
                     help="also run the steps on the same tree after giving it MAT local references (default when samples <= 200000)")
     ap.add_argument("--no-1m", action="store_true",
-                    help="skip the second leg of the default run (BASELINE configs[3]: 1 000 000 samples, full model)")
+                    help="skip the second leg of a --full run (BASELINE configs[3]: 1 000 000 samples, full model)")
     ap.add_argument("--steps-1m", type=int, default=3, help="timed steps of the 1 000 000-sample leg (131 072 searches each)")
     ap.add_argument("--online-add", type=int, default=50000,
                     help="BASELINE configs[4] on the 1 000 000-sample leg's tree (one GPU): this many new samples added one after the "
                          "other (placement search, tree edit, maple_update_partials, maple_tree_patch: M:11692-11752), then one round "
                          "of searches on the grown tree; 0 = skip")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 class Env:
@@ -321,15 +334,47 @@ def write_detail(full):
     return name
 
 
+DUMP_LIMIT = 64 << 20      # bytes: what --dump-outputs writes at most
+
+
+def dump_outputs(out_dir, nodes, res, moves, limit=DUMP_LIMIT):
+    """--dump-outputs: what the last timed step handed its caller, as out_dir/<name>.npy in float64 (node ids and counts are exact
+    in it): `nodes` (the pruned nodes this rank searched), the arrays spr_search_batch returned for them (one row per search) and
+    `moves` (the proposed moves as gather_proposals hands them on: [node, placement, improvement], sorted by improvement).  When
+    they would take more than `limit` bytes, the same fraction of rows is written from both -- a fixed, seeded sample (`rows`,
+    `moves_rows`: the row indices kept, ascending).  Returns the names written."""
+    per_search = {"nodes": nodes, **res}
+    per_search = {k: np.asarray(v, dtype=np.float64) for k, v in per_search.items()}
+    if isinstance(moves, np.ndarray):                   # (one rank: the step's own records [improvement, node, placement], unsorted)
+        moves = [(r[1], r[2], r[0]) for r in moves[np.argsort(moves[:, 0], kind="stable")]]
+    moves = np.asarray(moves, dtype=np.float64).reshape(-1, 3)
+    n, n_mv = len(per_search["nodes"]), len(moves)
+    total = sum(a.nbytes for a in per_search.values()) + moves.nbytes
+    arrays = dict(per_search, moves=moves)
+    budget = limit - (64 << 10)                            # (room for the .npy headers)
+    if total > budget:
+        frac = budget / (total + 8 * (n + n_mv))          # (the two index arrays count against the limit too)
+        rows = np.sort(np.random.default_rng(1).choice(n, size=int(frac * n), replace=False))
+        mv_rows = np.sort(np.random.default_rng(2).choice(n_mv, size=int(frac * n_mv), replace=False))
+        arrays = {k: a[rows] for k, a in per_search.items()}
+        arrays.update(moves=moves[mv_rows], rows=rows.astype(np.float64), moves_rows=mv_rows.astype(np.float64))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(arrays)
+
+
 def main():
     args = parse_args()
     env = init_env(args)
     out = run_leg(args, env)
-    # The default run has a second leg: BASELINE configs[3] -- the tree the metric's target is quoted on (1 000 000 samples, full
-    # model) -- on this one GPU, 131 072 searches per step (rotating through the tree's pre-order), its own roofline block.
+    # A --full run of the default workload has a second leg: BASELINE configs[3] -- the tree the metric's target is quoted on
+    # (1 000 000 samples, full model) -- on this one GPU, 131 072 searches per step (rotating through the tree's pre-order), its
+    # own roofline block.
     default_line = (args.samples, args.model, args.batch, args.spr_fast, args.tree) == (100000, "ratevar", 0, False, "optimised")
-    if default_line and not args.no_1m:
+    if args.full and default_line and not args.no_1m:
         a2 = argparse.Namespace(**vars(args))
+        a2.dump_outputs = None                           # (the outputs written are the headline's)
         # (three warm-up calls: the frontier tier's pools are sized by what the calls before asked for, and a call whose pools ran over
         # under-reports -- at this size they stop growing after the third call)
         a2.samples, a2.model, a2.batch, a2.steps, a2.warmup = 1000000, "siteerr", 131072, args.steps_1m, 3
@@ -506,14 +551,18 @@ def run_leg(args, env):
     elapsed_local = elapsed
     K = {name: dev.timing_read_kind(getattr(Device, "KIND_" + name)) for name in
          ("SPR_SCORE", "SPR_SEARCH", "SPR_REPLAY", "FR_UPDATING", "FR_CACHED", "FR_REPLAY", "FR_WIDE")}     # (launches, ms, units, bytes)
-    # what a caller pays for the first round after the tree changed: the tree uploaded again (every per-tree table of the library is
-    # dropped), then one step -- the pools are there, the tables are not
-    t_u = time.perf_counter()
-    upload_headline_tree()
-    reupload_ms = 1e3 * (time.perf_counter() - t_u)
-    t_u = time.perf_counter()
-    step(args.steps + args.warmup)
-    first_after_upload_ms = 1e3 * (time.perf_counter() - t_u)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, batch_of(args.steps - 1), res, moves)
+    reupload_ms = first_after_upload_ms = None
+    if args.full:
+        # what a caller pays for the first round after the tree changed: the tree uploaded again (every per-tree table of the library
+        # is dropped), then one step -- the pools are there, the tables are not
+        t_u = time.perf_counter()
+        upload_headline_tree()
+        reupload_ms = 1e3 * (time.perf_counter() - t_u)
+        t_u = time.perf_counter()
+        step(args.steps + args.warmup)
+        first_after_upload_ms = 1e3 * (time.perf_counter() - t_u)
     for res in kept:
         for k, v in zip(*np.unique(res["status"], return_counts=True)):
             status_counts[str(int(k))] = status_counts.get(str(int(k)), 0) + int(v)
@@ -547,7 +596,7 @@ def run_leg(args, env):
         per_rank = [None] * world
         distd.all_gather_object(per_rank, mine_ms)
     extras = {}
-    if not args.no_extras and rank == 0:
+    if args.full and not args.no_extras and rank == 0:
         extras = sub_blocks(args, dev, mirror, data, ref_idx, tip_kw, kw, order, B, upload_plain_tree, torch, cu,
                             first_step=kept[0] if kept else None, first_nodes=batch_of(0), headline_refs=(ht is not None))
 
@@ -697,7 +746,7 @@ def run_leg(args, env):
                                       "deep round: non-strict, allowedFailsTopology 4, thresholdLogLKtopology 14 log(lRef)")},
         }
         out.update(extras)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["tree_log_lk"] = tree_log_lk_check(dev, mirror, ht, tip_ids, mkw, ref_idx, root_freqs)
             if not out["tree_log_lk"]["rel_delta"] <= 1e-6:
                 raise SystemExit(f"tree log-LK: GPU and oracle differ by more than 1e-6 relative: {out['tree_log_lk']}")

@@ -237,6 +237,74 @@ def test_bench_line_is_small_and_follows_the_contract():
                 assert again[k] == v, k
 
 
+def test_bench_options():
+    """A plain `bench.py` run is the headline alone (--full off), --steps is the number of timed steps and at least one,
+    --dump-outputs names a directory."""
+    import bench
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert (a.gpus, a.steps, a.warmup, a.full, a.dump_outputs) == (1, 7, 2, False, None)
+    a = bench.parse_args(["--full", "--dump-outputs", "out"])
+    assert a.full is True and a.dump_outputs == "out"
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--steps", "0"])
+
+
+def _search_result(n, seed):
+    """Arrays shaped as Device.spr_search_batch returns them."""
+    rng = np.random.default_rng(seed)
+    return dict(bestNode=rng.integers(0, 2 * n, n).astype(np.int32), bestScore=rng.normal(size=n), blen=rng.random((n, 3)),
+                placement=np.where(rng.random(n) < 0.3, rng.integers(0, 2 * n, n), -1).astype(np.int32),
+                improvement=rng.random(n), currentLK=rng.normal(size=n), nAppend=rng.integers(0, 500, n).astype(np.int32),
+                status=rng.integers(-1, 1, n).astype(np.int32))
+
+
+def test_bench_dump_outputs(tmp_path):
+    """bench.dump_outputs (--dump-outputs): every array the last timed step returned, as float64 .npy files that hold the same
+    values, and the proposed moves in the form gather_proposals hands them on (what a run on N GPUs returns)."""
+    import bench
+    from maple_amd.parallel import gather_proposals, pack_proposals
+    n = 1000
+    res = _search_result(n, 0)
+    nodes = 2 * np.arange(n, dtype=np.int64)
+    rec = pack_proposals(nodes, res["placement"], res["improvement"])
+    names = bench.dump_outputs(str(tmp_path / "out"), nodes, res, rec)
+    assert sorted(names) == sorted(list(res) + ["nodes", "moves"])
+    got = {k: np.load(tmp_path / "out" / f"{k}.npy") for k in names}
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert np.array_equal(got["nodes"], nodes)
+    for k, v in res.items():
+        assert got[k].shape == v.shape and np.array_equal(got[k], v.astype(np.float64)), k
+    want = np.asarray(gather_proposals(rec), dtype=np.float64)
+    assert len(want) == int((res["placement"] >= 0).sum()) and np.array_equal(got["moves"], want)
+    assert np.all(np.diff(got["moves"][:, 2]) >= 0)
+
+
+def test_bench_dump_outputs_over_the_limit_is_a_fixed_sample(tmp_path):
+    """Over the size limit dump_outputs writes a seeded sample of the rows, the same rows of every per-search array, the same
+    sample from run to run, and stays within the limit (.npy headers included)."""
+    import bench
+    from maple_amd.parallel import pack_proposals
+    n = 5000
+    res = _search_result(n, 1)
+    nodes = np.arange(n, dtype=np.int64)
+    rec = pack_proposals(nodes, res["placement"], res["improvement"])
+    limit = (64 << 10) + 100000                             # (the data budget: 100 000 bytes of the 440 000 or so in full)
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), nodes, res, rec, limit=limit)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == sorted(os.listdir(tmp_path / "b"))
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= limit
+    for f in files:
+        assert open(tmp_path / "a" / f, "rb").read() == open(tmp_path / "b" / f, "rb").read(), f
+    rows = np.load(tmp_path / "a" / "rows.npy").astype(np.int64)
+    assert 0 < len(rows) < n and np.all(np.diff(rows) > 0)
+    assert np.array_equal(np.load(tmp_path / "a" / "nodes.npy"), nodes[rows].astype(np.float64))
+    for k, v in res.items():
+        assert np.array_equal(np.load(tmp_path / "a" / f"{k}.npy"), v[rows].astype(np.float64)), k
+    mv_rows = np.load(tmp_path / "a" / "moves_rows.npy").astype(np.int64)
+    assert 0 < len(mv_rows) < len(rec) and len(np.load(tmp_path / "a" / "moves.npy")) == len(mv_rows)
+
+
 def test_oracle_tree_log_lk_from_the_tips_equals_calculateTreeLikelihood_over_stored_lists(monkeypatch):
     """bench.oracle_tree_log_lk (the oracle's side of the metric's "tree log-LK delta": calculateTreeLikelihood from the tips'
     lists alone, M:9721-9779 over M:6031-6200) against tree_host.tree_log_likelihood over the lists a full build stored -- both

@@ -707,6 +707,36 @@ def test_bench_two_ranks_rccl():
     assert line2["config"]["candidate_placements_timed"] == line1["config"]["candidate_placements_timed"]
 
 
+def test_bench_plain_run_dumps_its_outputs(tmp_path):
+    """A plain `bench.py` run (no --full) on a small tree: the line has the contract's fields and nothing of what --full adds,
+    --steps timed steps, and --dump-outputs writes the last timed step's arrays in float64 -- the same files from run to run."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    common = ["--gpus", "1", "--samples", "1500", "--model", "unrest", "--batch", "600", "--steps", "3", "--warmup", "1"]
+    lines = []
+    for run in ("a", "b"):
+        p = subprocess.run([sys.executable, os.path.join(root, "bench.py")] + common + ["--dump-outputs", str(tmp_path / run)],
+                           capture_output=True, text=True, timeout=600, cwd=root)
+        assert p.returncode == 0, p.stderr[-2000:]
+        lines.append(json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1]))
+    line = lines[0]
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in line, k
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["value"] > 0
+    assert line["config"]["searches_timed"] == 3 * 600
+    assert "cpu_baseline" not in line and "tree_log_lk" not in line and line["first_step_after_upload_ms"] is None
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert "placement.npy" in files and "moves.npy" in files and files == sorted(os.listdir(tmp_path / "b"))
+    nodes = np.load(tmp_path / "a" / "nodes.npy")
+    assert nodes.dtype == np.float64 and len(nodes) == 600
+    for f in files:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype == np.float64 and np.array_equal(a, b, equal_nan=True), f
+
+
 def test_apply_phase_batched_equals_sequential(world):
     """applySPRMovesParallel (M:9470-9484) in its two drivers (maple_amd/spr_apply.py): the proposed moves of a deep round on a
     tree with misplaced tips, re-searched one at a time on the current tree and applied -- against the same moves re-searched

@@ -5,8 +5,8 @@
 # profiles/<NAME>.md, profiles/<NAME>_kernel_stats.csv and the PMC json bench.py reads for `traffic`.
 R=${GRAFT_REPO_ROOT:-/root/repo}; NAME=$1; EXTRA=$2
 OUT=$R/gpurun_out/$NAME; mkdir -p $OUT; cd /tmp; export TMPDIR=/tmp
-B="python $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-extras $EXTRA"
-python $R/bench.py $EXTRA > $OUT/bench.json 2> $OUT/bench.err
+B="python $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-extras $EXTRA"
+python $R/bench.py --full $EXTRA > $OUT/bench.json 2> $OUT/bench.err
 rocprofv3 --kernel-trace --stats -f csv -d $OUT/stats -- $B > $OUT/stats.log 2>&1
 rocprofv3 --pmc FETCH_SIZE -f csv -d $OUT/fetch -- $B > $OUT/fetch.log 2>&1
 rocprofv3 --pmc WRITE_SIZE -f csv -d $OUT/write -- $B > $OUT/write.log 2>&1

@@ -6,8 +6,8 @@
 R=${GRAFT_REPO_ROOT:-/root/repo}; NAME=$1; EXTRA=$2; COMMIT=$3
 # (the traced and counted runs leave out the 1 000 000-sample leg of the default line; the un-profiled bench line has it)
 OUT=$R/gpurun_out/$NAME; mkdir -p $OUT; cd /tmp; export TMPDIR=/tmp
-B="python $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-extras --no-1m $EXTRA"
-python $R/bench.py $EXTRA > $OUT/bench.json 2> $OUT/bench.err; cp $R/bench_detail.json $OUT/bench_detail.json
+B="python $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-extras --no-1m $EXTRA"
+python $R/bench.py --full $EXTRA > $OUT/bench.json 2> $OUT/bench.err; cp $R/bench_detail.json $OUT/bench_detail.json
 rocprofv3 --kernel-trace --stats -f csv -d $OUT/stats -- $B > $OUT/stats.log 2>&1
 rocprofv3 --pmc FETCH_SIZE -f csv -d $OUT/fetch -- $B > $OUT/fetch.log 2>&1
 rocprofv3 --pmc WRITE_SIZE -f csv -d $OUT/write -- $B > $OUT/write.log 2>&1

@@ -21,9 +21,9 @@ def main():
     note = sys.argv[6] if len(sys.argv) > 6 else ""
     out = [f"# profiles/{name}\n\n"]
     out.append("rocprofv3 passes (run from /tmp with TMPDIR=/tmp on the MI355X box; counters in their own passes):\n\n")
-    out.append("    rocprofv3 --kernel-trace --stats -f csv -d <dir> -- python bench.py --steps 20 --warmup 3 --no-cpu-baseline\n")
-    out.append("    rocprofv3 --pmc FETCH_SIZE -f csv -d <dir> -- python bench.py --steps 5 --warmup 1 --no-cpu-baseline\n")
-    out.append("    rocprofv3 --pmc WRITE_SIZE -f csv -d <dir> -- python bench.py --steps 5 --warmup 1 --no-cpu-baseline\n\n")
+    out.append("    rocprofv3 --kernel-trace --stats -f csv -d <dir> -- python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline\n")
+    out.append("    rocprofv3 --pmc FETCH_SIZE -f csv -d <dir> -- python bench.py --full --steps 5 --warmup 1 --no-cpu-baseline\n")
+    out.append("    rocprofv3 --pmc WRITE_SIZE -f csv -d <dir> -- python bench.py --full --steps 5 --warmup 1 --no-cpu-baseline\n\n")
     out.append("## kernel_stats.csv (top rows)\n\n| kernel | calls | total ns | avg ns | % | min ns | max ns |\n|---|---|---|---|---|---|---|\n")
     for i, r in enumerate(csv.DictReader(open(one(stats_dir + "/*/*_kernel_stats.csv")))):
         if i >= 8:

@@ -33,8 +33,8 @@ def base(k):
 
 lines = [f"# profiles/{name}\n\n"]
 lines.append("Commands (MI355X box, from /tmp with TMPDIR=/tmp; counters in their own passes, never with a trace):\n\n")
-lines.append(f"    python bench.py {extra}                                              # the bench line below\n")
-lines.append(f"    rocprofv3 --kernel-trace --stats -f csv -- python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-extras {extra}\n")
+lines.append(f"    python bench.py --full {extra}                                              # the bench line below\n")
+lines.append(f"    rocprofv3 --kernel-trace --stats -f csv -- python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-extras {extra}\n")
 lines.append("    rocprofv3 --pmc FETCH_SIZE | WRITE_SIZE | SQ_* | SQ_LDS_* GRBM_GUI_ACTIVE -f csv -- (the same command)\n\n")
 try:
     bench = json.loads([ln for ln in open(os.path.join(out, "bench.json")) if ln.startswith("{")][-1])
