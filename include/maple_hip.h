@@ -323,12 +323,16 @@ int maple_placement_prepare(maple_ctx *ctx, const maple_placement_params *params
  * tables; 0 on a tree with MAT reference frames, where the call changes nothing); announce the rest when those are done.
  * The rows hold the branches an expansion of all announced samples under permissive rules reaches (every branch the
  * reference's traversal can visit on the tree as it is then; maple_tuning.noAheadExpansion: every branch of the tree).
+ * A list rewritten with maple_lists_update keeps its id: the columns that read it are scored again like changed ones.
  * While rows live, the library runs the traversal of the NEXT announced sample in a host thread of its own as soon as a search
- * has finished its own -- on library-owned memory only, joined at the start of maple_tree_patch and of every call that could
- * change what it reads; it is used if the patch in between touched no node it had visited (maple_tuning.noAheadSpeculation
- * switches it off).
+ * has finished its own -- on library-owned memory only, joined (and what it made not used) at the start of maple_tree_patch,
+ * maple_lists_update, maple_set_model, maple_set_tuning, maple_tree_upload, maple_arena_compact and maple_destroy, of a
+ * maple_placement_prepare that makes the placement tables anew, and of a maple_arena_release of a list it reads; it is used if
+ * the patch in between touched no node it had visited (maple_tuning.noAheadSpeculation switches it off).
  * The rows are dropped by anything that renumbers the columns or changes what a score means (maple_tree_upload,
- * maple_set_model, other parameters, a release of the samples' lists), and by a search of any other sample. */
+ * maple_set_model, a maple_placement_prepare or search with another effectivelyNon0BLen, a search of more than four samples on
+ * a patched tree, a release of the samples' lists).  A search of a sample that is not the next announced one, or with other
+ * parameters, is the plain search and leaves the rows as they are: the next announced sample still takes its row. */
 int maple_placement_ahead(maple_ctx *ctx, int32_t nQ, const int32_t *qLists, const maple_placement_params *params, int32_t *nTaken);
 /* What the rows made ahead were used for since the context was created: out5 = searches that took a row, those among them whose
  * row had to be scored in full after all (the traversal asked for a branch the expansion had not reached), items the

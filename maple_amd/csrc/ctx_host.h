@@ -297,6 +297,14 @@ struct maple_ctx {
     DevBuf<double> s_trace_d;
 };
 
+// The traversal made ahead of its search (PlaceAhead::Spec) runs in a host thread of the library and reads the arena's lists, the
+// model and the placement tables: an entry point that writes what it reads calls this first -- the thread is joined, and what it
+// made is not used (the search makes that traversal itself).
+static inline void ahead_quiesce(maple_ctx *c)
+{
+    if (c && c->ahead) { c->ahead->join(); c->ahead->spec.row = -1; }
+}
+
 enum { MAPLE_K_OTHER = 0, MAPLE_K_SPR_SCORE = 1, MAPLE_K_SPR_SEARCH = 2, MAPLE_K_SPR_REPLAY = 3, MAPLE_K_APPEND_QUERIES = 4,
        MAPLE_K_APPEND_PAIRS = 5, MAPLE_K_PLACE_SCORE = 6, MAPLE_K_FR_UPDATING = 7, MAPLE_K_FR_CACHED = 8, MAPLE_K_FR_REPLAY = 9,
        MAPLE_K_FR_WIDE = 10 };

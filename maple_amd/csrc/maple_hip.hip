@@ -1012,6 +1012,7 @@ extern "C" int maple_set_tuning(maple_ctx *c, const maple_tuning *t)
     if (t->structSize < sizeof(uint32_t) + sizeof(int32_t)) return fail(c, MAPLE_ERR_ARG, "maple_set_tuning: structSize is not set (sizeof(maple_tuning) of the caller's header)");
     const int32_t verbose = c->tuning.verbose;
     maple_tuning mine{};                                              // (what the caller's struct does not reach keeps the library's choice)
+    ahead_quiesce(c);
     memcpy(&mine, t, std::min<size_t>(t->structSize, sizeof(maple_tuning)));
     mine.structSize = (uint32_t)sizeof(maple_tuning);
     c->tuning = mine;
@@ -1022,6 +1023,7 @@ extern "C" int maple_set_tuning(maple_ctx *c, const maple_tuning *t)
 extern "C" int maple_destroy(maple_ctx *c)
 {
     if (!c) return MAPLE_OK;
+    ahead_quiesce(c);                                                   // (the library's own thread reads what is freed below)
     // this context's device first, and nothing in flight on any of its streams, before anything is freed
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
@@ -1074,7 +1076,8 @@ extern "C" int maple_set_model(maple_ctx *c, const double *Q16, const double *si
     DevModel &m = c->dm;
     const int lRef = c->lRef;
     c->h_over_hint.clear();                                           // (which searches run over the budget is a property of the model too)
-    if (c->ahead) { c->ahead->join(); c->ahead->spec.row = -1; c->ahead->active = false; }   // (rows scored under another model)
+    ahead_quiesce(c);
+    if (c->ahead) c->ahead->active = false;                             // (rows scored under another model)
     for (int i = 0; i < 16; i++) m.Q[i] = Q16[i];
     m.useRateVariation = siteRates ? 1 : 0;
     m.usingErrorRate = usingErrorRate ? 1 : 0;
@@ -1279,8 +1282,18 @@ extern "C" int maple_arena_release(maple_ctx *c, int64_t markBoth)
         c->h_mut_off.resize(mmark); c->h_mut_cnt.resize(mmark);
     }
     if (mark == (int64_t)c->h_n_ent.size()) return MAPLE_OK;
-    if (c->ahead && c->ahead->active)                                   // (rows of samples whose lists go with the release)
-        for (int32_t id : c->ahead->q) if (id >= mark) { c->ahead->active = false; break; }
+    if (c->ahead) {
+        // the traversal made ahead reads its sample's list and the lists of the columns it scores: if one of them goes with the
+        // release, the thread is joined before the room can be written again (a release above them -- the per-search mark of the
+        // serial loop -- leaves it running)
+        PlaceAhead &A = *c->ahead;
+        bool reads = A.spec.row >= 0 && A.spec.row < (int32_t)A.q.size() && A.q[A.spec.row] >= mark;
+        for (size_t i = 0; !reads && A.spec.row >= 0 && i < A.spec.lists.size(); i++) reads = A.spec.lists[i] >= mark;
+        for (size_t i = 0; !reads && A.spec.row >= 0 && i < A.spec.leafLists.size(); i++) reads = A.spec.leafLists[i] >= mark;
+        if (reads) ahead_quiesce(c);
+        if (A.active)                                                   // (rows of samples whose lists go with the release)
+            for (int32_t id : A.q) if (id >= mark) { A.active = false; ahead_quiesce(c); break; }
+    }
     if (mark < c->cand_root_end) c->cand_root_end = -1;                 // (the candidates' root-frame copies go with the release)
     if (mark < c->cand_root_top) c->cand_root_mark = c->cand_root_top = -1;
     int64_t ue = c->h_ent_off[mark], ua = c->h_aux_off[mark];
@@ -1310,7 +1323,8 @@ static int grid_for(int n);
 // replaced list keeps its room until then.
 extern "C" int maple_arena_compact(maple_ctx *c, int64_t nLive, const int32_t *live, int32_t *newIds)
 {
-    if (c && c->ahead) { c->ahead->join(); c->ahead->spec.row = -1; c->ahead->active = false; }
+    ahead_quiesce(c);
+    if (c && c->ahead) c->ahead->active = false;
     if (!c || nLive < 0 || (nLive && (!live || !newIds))) return MAPLE_ERR_ARG;
     HIPCK(c, hipSetDevice(c->device));
     TRY(settle(c));
@@ -1486,6 +1500,29 @@ __global__ void k_set_rows(int n, const int32_t *ids, const int64_t *eo, const i
     if (i < n) { const int r = ids[i]; t_ent_off[r] = eo[i]; t_aux_off[r] = ao[i]; t_n_ent[r] = ne[i]; t_n_aux[r] = na[i]; }
 }
 
+// maple_lists_update keeps ids: the placement search's columns that read one of the rewritten lists score something new.  Score rows
+// made ahead note them as changed (maple_tree_patch does the same for the nodes it is given), and the root vector of a rewritten
+// root list is made again.
+static void lists_update_mark_rows(maple_ctx *c, int32_t n, const int32_t *ids)
+{
+    if (!c->place || !c->place->valid || !c->tree_set) return;
+    PlaceMeta &M = *c->place;
+    std::vector<int32_t> s(ids, ids + n);
+    std::sort(s.begin(), s.end());
+    auto has = [&](int32_t id) { return id >= 0 && std::binary_search(s.begin(), s.end(), id); };
+    PlaceAhead *const ah = (c->ahead && c->ahead->active) ? c->ahead : nullptr;
+    const int32_t root = c->dtree.root;
+    if (root >= 0 && (size_t)root < c->h_tree_lower.size() && has(c->h_tree_lower[root])) {
+        M.rootVect = -1;
+        if (ah) ah->rootDirty = true;
+    }
+    if (!ah) return;
+    for (size_t col = 0; col < M.h_candList.size(); col++)
+        if (has(M.h_candList[col])) { if ((int64_t)col >= ah->ld - 1) ah->active = false; else ah->dirtyCols.push_back((int32_t)col); }
+    for (size_t lc = 0; lc < M.h_leafList.size(); lc++)
+        if (has(M.h_leafList[lc])) { if ((int64_t)lc >= ah->ldL) ah->active = false; else ah->dirtyLeaves.push_back((int32_t)lc); }
+}
+
 // New contents for EXISTING lists: ids[i] keeps its number (every table that refers to it -- tree columns, candidate sets,
 // an uploaded tree -- stays valid) and from now on names the new words.  A list that fits in the room of the old one is
 // overwritten in place; otherwise it gets fresh room at the end of the arena (the old room is given back by the next
@@ -1497,6 +1534,8 @@ extern "C" int maple_lists_update(maple_ctx *c, int32_t n, const int32_t *ids, c
     if (n == 0) return MAPLE_OK;
     HIPCK(c, hipSetDevice(c->device));
     TRY(check_ids(c, n, ids, false, "list"));
+    ahead_quiesce(c);                                                   // (the words of a list the library's thread may be reading)
+    lists_update_mark_rows(c, n, ids);
     std::vector<int64_t> eo(n), ao(n);
     std::vector<int32_t> cnt(n), cna(n);
     int64_t ue = c->used_ent, ua = c->used_aux;

@@ -266,6 +266,7 @@ extern "C" int maple_placement_prepare(maple_ctx *c, const maple_placement_param
     HIPCK(c, hipSetDevice(c->device));
     TRY(need_model(c));
     if (!c->tree_set) return fail(c, MAPLE_ERR_STATE, "maple_tree_upload has not been called");
+    if (!c->place->valid || c->place->effNon0 != pp->effectivelyNon0BLen) ahead_quiesce(c);   // (the tables below are made anew)
     if (c->tree_stale && (!c->place->valid || c->place->effNon0 != pp->effectivelyNon0BLen)) TRY(tree_rebuild_from_host(c));
     TRY(place_meta(c, pp->effectivelyNon0BLen));
     PlaceMeta &M = *c->place;
@@ -945,7 +946,9 @@ static int placement_search_impl(maple_ctx *c, int32_t nQ, const int32_t *qLists
                     // elsewhere): every branch scored for this sample, as the plain search does, and once more
                     TRY(launch_append_queries(c, c->stream, 1, ah->dQ.p + ah->next, nC, M.d_candList.p, 1, pp->oneMutBLen,
                                               ah->dTable.p + (size_t)ah->next * ah->ld, ah->ld, nullptr, nullptr, nullptr, MAPLE_K_PLACE_SCORE, 0.0));
-                    HIPCK(c, hipMemcpyAsync(hs, ah->dTable.p + (size_t)ah->next * ah->ld, (size_t)ah->ld * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+                    // (only the nC columns scored now come back: the root's column of the host row is the one ahead_refresh made
+                    // current, the device row still holds the one of the batch's start)
+                    HIPCK(c, hipMemcpyAsync(hs, ah->dTable.p + (size_t)ah->next * ah->ld, (size_t)nC * sizeof(double), hipMemcpyDeviceToHost, c->stream));
                     HIPCK(c, hipStreamSynchronize(c->stream));
                     ah->fallbacks++;
                     place_replay_ptr(c, M, P, hs, rootCol, hm, nF, oq, false);

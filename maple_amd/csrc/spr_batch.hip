@@ -394,7 +394,8 @@ extern "C" int maple_tree_upload(maple_ctx *c, int32_t n, int32_t root, const in
         || !totUp || !mutList)
         return MAPLE_ERR_ARG;
     HIPCK(c, hipSetDevice(c->device));
-    if (c->ahead) { c->ahead->join(); c->ahead->spec.row = -1; c->ahead->active = false; }
+    ahead_quiesce(c);
+    if (c->ahead) c->ahead->active = false;
     const bool dbgU = c->tuning.verbose != 0;
     auto tU0 = std::chrono::steady_clock::now();
     auto lapU = [&](const char *what) {
@@ -756,7 +757,10 @@ extern "C" int maple_tree_patch(maple_ctx *c, int32_t nTotal, int32_t nTouched, 
         const bool cand = v != root && up[i] >= 0 && dist[i] > M.effNon0 && totUp[i] >= 0;        // M:8049
         int col = M.h_candIdx[v];
         if (col >= 0 && !cand) M.h_candIdx[v] = -1;                       // (the column stays and is scored for nothing)
-        else if (col >= 0) { if (M.h_candList[col] != totUp[i]) { M.h_candList[col] = totUp[i]; TRY(poke(M.d_candList, col, totUp[i])); dirty_col(col); } }
+        else if (col >= 0) {                                              // (dirty whatever the id: maple_lists_update keeps ids)
+            if (M.h_candList[col] != totUp[i]) { M.h_candList[col] = totUp[i]; TRY(poke(M.d_candList, col, totUp[i])); }
+            dirty_col(col);
+        }
         else if (cand) {
             col = (int)M.cand.size();                                     // the column of the root vector moves up by one
             M.cand.push_back(v);
@@ -775,7 +779,10 @@ extern "C" int maple_tree_patch(maple_ctx *c, int32_t nTotal, int32_t nTouched, 
         if (lc >= 0 && !leaf) M.h_leafIdx[v] = -1;
         else if (leaf) {
             if (lower[i] < 0) { (void)flush_pokes(); return settle_patch(fail(c, MAPLE_ERR_STATE, "leaf %d has no lower genome list", v)); }
-            if (lc >= 0) { if (M.h_leafList[lc] != lower[i]) { M.h_leafList[lc] = lower[i]; TRY(poke(M.d_leafList, lc, lower[i])); dirty_leaf(lc); } }
+            if (lc >= 0) {
+                if (M.h_leafList[lc] != lower[i]) { M.h_leafList[lc] = lower[i]; TRY(poke(M.d_leafList, lc, lower[i])); }
+                dirty_leaf(lc);
+            }
             else {
                 lc = (int)M.leaves.size();
                 M.leaves.push_back(v);

@@ -129,6 +129,33 @@ int omo_sprWorker(const OModel *m, const OTree *t, const OSearchParams *p, int n
 int omo_sprWorker_mt(const OModel *m, const OTree *t, const OSearchParams *p, int n, const int *nodes, OSearchResult *out,
                      void *arenaMem, size_t arenaBytesPerThread, int threads);
 
+/* ---- sample placement (oracle/maple_oracle_search.c) ------------------------------------------------------------ */
+/* isMinorSequence(probVect1, probVect2, onlyFindIdentical), M:5918-6003: 0 not comparable, 1 the first is more
+ * informative or identical, 2 the second is; -1 where the reference would index past a list's end */
+int omo_isMinorSequence(const OModel *m, const OEntry *pv1, int n1, const OEntry *pv2, int n2, int onlyFindIdentical);
+
+typedef struct {
+    int strict, allowedFails, onlyFindIdentical;
+    double oneMutBLen, thrLK, thrOpt, thrConsec, effNon0;  /* thresholdLogLK, thresholdLogLKoptimization,
+                                                               thresholdLogLKconsecutivePlacement, effectivelyNon0BLen */
+} OPlaceParams;
+
+typedef struct {
+    int status;                          /* 0 placed, 1 a minor sequence of bestNode (the reference returns 1.0, None) */
+    int bestNode, nAppend;               /* nAppend: appendProbNode calls, as tests/golden/make_golden_search.py counts */
+    int blenNone;                        /* 1: the reference's branch lengths are None                              */
+    double bestScore;
+    double blen[3];                      /* top, bottom, appending; the reference's False is 0.0                    */
+    OEntry *diffs;                       /* optional caller buffer for bestDiffs                                    */
+    int diffsCap, diffsN;
+} OPlaceResult;
+
+/* findBestParentForNewSample(tree, root, query, sample, computePlacementSupportOnly=False), M:7912-8292, without
+ * HnZ, time trees and --deeperSearchForLongBranches.  The tree is not modified (a minor sequence is reported, not
+ * appended).  0 ok, -1 the reference raises, -3 arena too small, -4 res->diffs too small */
+int omo_findBestParentForNewSample(const OModel *m, const OTree *t, const OPlaceParams *p, const OEntry *query, int nQuery,
+                                   OPlaceResult *res, void *arenaMem, size_t arenaBytes);
+
 /* batch driver (lists concatenated, off[] = CSR offsets by list index) used to time the CPU baseline */
 int   omo_appendProbNode_batch(const OModel *m, const OEntry *all, const long long *off, int n, const int *pl,
                                const int *cl, const unsigned char *tip, const double *bl, double *out);

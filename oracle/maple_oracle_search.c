@@ -420,3 +420,190 @@ int omo_sprWorker_mt(const OModel *m, const OTree *t, const OSearchParams *p, in
     }
     return 0;
 }
+
+/* ---- isMinorSequence, M:5918-6003 -------------------------------------------------------------------------------- */
+int omo_isMinorSequence(const OModel *m, const OEntry *pv1, int n1, const OEntry *pv2, int n2, int onlyFindIdentical)
+{
+    const int lRef = m->lRef;
+    int i1 = 0, i2 = 0, pos = 0, found1 = 0, found2 = 0;
+    if (n1 <= 0 || n2 <= 0) return -1;                              /* (an empty list: the reference would raise) */
+    for (;;) {
+        const OEntry *e1 = &pv1[i1], *e2 = &pv2[i2];
+        if (e1->type != e2->type) {
+            if (onlyFindIdentical) return 0;
+            if (e1->type == 5) {
+                if (e2->type == 4) pos = e1->x < e2->x ? e1->x : e2->x;
+                else pos++;
+                found2 = 1;
+            } else if (e2->type == 5) {
+                if (e1->type == 4) pos = e1->x < e2->x ? e1->x : e2->x;
+                else pos++;
+                found1 = 1;
+            } else if (e1->type == 6) {
+                const int k = e2->type == 4 ? e1->x : e2->type;
+                if (e1->vec[k] > 0.1) found2 = 1;
+                else return 0;
+                pos++;
+            } else if (e2->type == 6) {
+                const int k = e1->type == 4 ? e2->x : e1->type;
+                if (e2->vec[k] > 0.1) found1 = 1;
+                else return 0;
+                pos++;
+            } else return 0;
+        } else if (e1->type == 6) {
+            for (int j = 0; j < 4; j++) {
+                if (onlyFindIdentical) {
+                    if (e2->vec[j] != e1->vec[j]) return 0;
+                } else if (e2->vec[j] > 0.1 && e1->vec[j] < 0.1) found1 = 1;
+                else if (e1->vec[j] > 0.1 && e2->vec[j] < 0.1) found2 = 1;
+            }
+            pos++;
+        } else if (e1->type < 4) pos++;
+        else pos = e1->x < e2->x ? e1->x : e2->x;
+        if (found1 && found2) return 0;
+        if (pos == lRef) break;
+        if (e1->type < 4 || e1->type == 6 || pos == e1->x) i1++;
+        if (e2->type < 4 || e2->type == 6 || pos == e2->x) i2++;
+        if (i1 >= n1 || i2 >= n2) return -1;                          /* the reference's IndexError */
+    }
+    if (found1) return found2 ? 0 : 1;
+    return found2 ? 2 : 1;
+}
+
+/* ---- findBestParentForNewSample, M:7912-8292 (computePlacementSupportOnly=False) --------------------------------- */
+typedef struct { int t1, fails; double parentLK; OL *diffs; } PItem;
+typedef struct { int t1; double score; OL *diffs; } PRec;
+
+int omo_findBestParentForNewSample(const OModel *m, const OTree *t, const OPlaceParams *p, const OEntry *query, int nQuery,
+                                   OPlaceResult *res, void *arenaMem, size_t arenaBytes)
+{
+    OArena A = {(char *)arenaMem, arenaBytes, 0, 0};
+    OS S = {m, t, NULL, &A, NULL, 0};
+    S.scratch = (double *)oa_alloc(&A, 65536 * sizeof(double));
+    const int capI = 1 << 16, capR = 1 << 16;
+    PItem *st = (PItem *)oa_alloc(&A, (size_t)capI * sizeof(PItem));
+    PRec *rec = (PRec *)oa_alloc(&A, (size_t)capR * sizeof(PRec));
+    OL *diffs = ol_new(&A, nQuery);                   /* a private object: shorten() edits it in place */
+    if (!S.scratch || !st || !rec || !diffs) return -3;
+    memcpy(diffs->e, query, (size_t)nQuery * sizeof(OEntry));
+    diffs->n = nQuery;
+    res->status = 0; res->nAppend = 0; res->blenNone = 0; res->diffsN = 0;
+    const int root = t->root;
+    int sp = 0, nR = 0, bestNode = root;
+    double bl[3] = {0.0, 0.0, p->oneMutBLen};                        /* (False, False, oneMutBLen) */
+    diffs = pass(&S, diffs, root, 0);
+    if (!diffs) return -3;
+    OL *bestDiffs = diffs;
+    if (t->c0[root] < 0) {                                           /* M:7936-7952 */
+        OL *pv = tree_list(&S, 0, root);
+        const int cmp = pv ? omo_isMinorSequence(m, pv->e, pv->n, diffs->e, diffs->n, p->onlyFindIdentical) : 0;
+        if (cmp < 0) return -1;                                      /* the reference raises */
+        if (cmp == 1) {
+            res->status = 1; bestNode = root;
+            goto minor;
+        }
+    }
+    OL *rootVect = root_vector(&S, tree_list(&S, 0, root), 0.0, 0, root);
+    if (!rootVect) return A.failed ? -3 : -1;
+    double bestLKdiff = append(&S, rootVect, diffs, 1, p->oneMutBLen);
+    const double originalLKdiff = bestLKdiff;
+    for (int k = 0; k < 2; k++) {                                    /* M:7964-7968 */
+        const int ch = k == 0 ? t->c0[root] : t->c1[root];
+        if (ch < 0) continue;
+        if (sp >= capI) return -3;
+        PItem it = {ch, 0, bestLKdiff, pass(&S, diffs, ch, 0)};
+        st[sp++] = it;
+    }
+    while (sp > 0) {                                                 /* M:7969-8103 */
+        if (A.failed) return -3;
+        PItem it = st[--sp];
+        const int t1 = it.t1;
+        int fails = it.fails;
+        OL *d = it.diffs;
+        double LKdiff;
+        if (t->c0[t1] < 0) {                                         /* M:7971-8008 */
+            OL *pv = tree_list(&S, 0, t1);
+            const int cmp = pv ? omo_isMinorSequence(m, pv->e, pv->n, d->e, d->n, p->onlyFindIdentical) : 0;
+            if (cmp < 0) { res->nAppend = S.nAppend; return -1; }       /* the reference raises */
+            if (cmp == 1) {
+                res->status = 1; bestNode = t1; bestDiffs = d;
+                goto minor;
+            }
+        }
+        if (t->dist[t1] > p->effNon0 && t->up[t1] >= 0) {             /* M:8010-8090, no deeper search */
+            OL *tot = tree_list(&S, 3, t1);
+            if (!tot) return -1;
+            LKdiff = append(&S, tot, d, 1, p->oneMutBLen);
+            if (LKdiff >= bestLKdiff) {
+                shorten_inplace(&S, d);
+                bestLKdiff = LKdiff; bestNode = t1; fails = 0;
+                if (nR >= capR) return -3;
+                PRec r = {t1, LKdiff, d}; rec[nR++] = r;
+                bestDiffs = d;
+                bl[0] = t->dist[t1] / 2; bl[1] = t->dist[t1] / 4; bl[2] = p->oneMutBLen;
+            } else if (LKdiff > bestLKdiff - p->thrOpt) {
+                if (nR >= capR) return -3;
+                PRec r = {t1, LKdiff, d}; rec[nR++] = r;
+            }
+            if (LKdiff < it.parentLK - p->thrConsec) fails++;
+        } else LKdiff = it.parentLK;
+        int go;
+        if (p->strict) go = fails <= p->allowedFails && LKdiff > bestLKdiff - p->thrLK;
+        else go = fails <= p->allowedFails || LKdiff > bestLKdiff - p->thrLK;
+        if (go)
+            for (int k = 0; k < 2; k++) {
+                const int ch = k == 0 ? t->c0[t1] : t->c1[t1];
+                if (ch < 0) continue;
+                if (sp >= capI) return -3;
+                PItem c = {ch, fails, LKdiff, pass(&S, d, ch, 0)};
+                st[sp++] = c;
+            }
+    }
+    /* refinement, M:8109-8187 (compensanteForBranchLengthChange) */
+    double bestScore = bestLKdiff;
+    for (int i = 0; i < nR; i++) {
+        if (A.failed) return -3;
+        if (!(rec[i].score >= bestLKdiff - p->thrOpt)) continue;
+        const int node = rec[i].t1, upN = t->up[node];
+        OL *upVect = pass(&S, tree_list(&S, t->c0[upN] == node ? 1 : 2, upN), node, 0);
+        OL *d = rec[i].diffs, *down = tree_list(&S, 0, node), *tot = tree_list(&S, 3, node);
+        if (!upVect || !down || !tot) return -1;
+        const int isTip = is_tip(t, node);
+        const size_t save = A.used;
+        const double app = blen(&S, tot, d, 1);
+        OL *midLower = merge(&S, down, t->dist[node] / 2, isTip, d, app, 1, 0);
+        if (!midLower) return -1;
+        const double top = blen(&S, upVect, midLower, 0);
+        OL *midTop = merge(&S, upVect, top, 0, d, app, 1, 1);
+        if (!midTop) return -1;
+        const double bottom = blen(&S, midTop, down, isTip);
+        OL *newMid = merge(&S, upVect, top, 0, down, bottom, isTip, 1);
+        if (!newMid) return -1;
+        const double cost = append(&S, newMid, d, 1, app);
+        const double initialCost = append(&S, upVect, down, isTip, t->dist[node]);
+        const double newPartialCost = append(&S, upVect, down, isTip, bottom + top);
+        const double optimized = cost + newPartialCost - initialCost;
+        A.used = save;
+        if (optimized >= bestScore) {
+            bestNode = node; bestScore = optimized;
+            bl[0] = top; bl[1] = bottom; bl[2] = app;
+            bestDiffs = d;
+        }
+    }
+    if (A.failed) return -3;
+    if (isinf(bestScore) && bestScore < 0) bestScore = originalLKdiff;
+    res->bestNode = bestNode; res->bestScore = bestScore;
+    res->blen[0] = bl[0]; res->blen[1] = bl[1]; res->blen[2] = bl[2];
+    goto out;
+minor:                                                              /* return t1, 1.0, None, diffs */
+    res->bestNode = bestNode; res->bestScore = 1.0; res->blenNone = 1;
+    res->blen[0] = res->blen[1] = res->blen[2] = 0.0;
+out:
+    res->nAppend = S.nAppend;
+    if (res->diffs) {
+        if (bestDiffs->n > res->diffsCap) return -4;
+        memcpy(res->diffs, bestDiffs->e, (size_t)bestDiffs->n * sizeof(OEntry));
+        res->diffsN = bestDiffs->n;
+    }
+    return 0;
+}

@@ -106,6 +106,18 @@ class OSearchParamsC(C.Structure):
                 ("effNon0", C.c_double), ("defaultBLen", C.c_double)]
 
 
+class OPlaceParamsC(C.Structure):
+    _fields_ = [("strict", C.c_int), ("allowedFails", C.c_int), ("onlyFindIdentical", C.c_int),
+                ("oneMutBLen", C.c_double), ("thrLK", C.c_double), ("thrOpt", C.c_double), ("thrConsec", C.c_double),
+                ("effNon0", C.c_double)]
+
+
+class OPlaceResultC(C.Structure):
+    _fields_ = [("status", C.c_int), ("bestNode", C.c_int), ("nAppend", C.c_int), ("blenNone", C.c_int),
+                ("bestScore", C.c_double), ("blen", C.c_double * 3), ("diffs", C.c_void_p), ("diffsCap", C.c_int),
+                ("diffsN", C.c_int)]
+
+
 class OSearchResultC(C.Structure):
     _fields_ = [("bestNode", C.c_int), ("placement", C.c_int), ("status", C.c_int), ("nAppend", C.c_int),
                 ("bestScore", C.c_double), ("improvement", C.c_double), ("currentLK", C.c_double),
@@ -163,7 +175,8 @@ def packed_to_entries(pk, u, threads=None):
 class OracleTree:
     """A frozen tree in the oracle's layout: topology + the four genome lists of every node (tuple form or None)."""
 
-    def __init__(self, oracle, root, up, children, dist, mutations, n_minor, lists4):
+    def __init__(self, oracle, root, up, children, dist, mutations, n_minor, lists4, headroom=0):
+        """headroom: entries of room behind the tree's own, for update() to append into."""
         u = oracle.u
         n = len(up)
         self.n = n
@@ -199,7 +212,13 @@ class OracleTree:
                         chunks.append(arr)
             self.start.append(st)
             self.len.append(ln)
-        self.ent = np.concatenate(chunks) if chunks else np.zeros(1, dtype=OENTRY)
+        self.n_ent = tot
+        self.ent = np.zeros(max(1, tot + int(headroom)), dtype=OENTRY)
+        at = 0
+        for ch in chunks:
+            self.ent[at: at + len(ch)] = ch
+            at += len(ch)
+        del chunks
         off = np.zeros(n + 1, dtype=np.int64)
         flat = []
         if mutations is not None:                                 # (None: a tree without MAT local references)
@@ -217,6 +236,88 @@ class OracleTree:
             t.len[k] = self.len[k].ctypes.data
         t.mut3, t.mutOff = _p(self.mut3), _p(self.mutOff)
         self.c = t
+
+    def _grow_nodes(self, n):
+        """Room for n nodes in the per-node columns (start/len keep their entries; new nodes have no lists)."""
+        if n <= len(self.start[0]):
+            return
+        cap = max(n, int(len(self.start[0]) * 1.25) + 1024)
+        for k in range(4):
+            st = np.zeros(cap, dtype=np.int64)
+            ln = np.zeros(cap, dtype=np.int32)
+            st[: len(self.start[k])] = self.start[k]
+            ln[: len(self.len[k])] = self.len[k]
+            self.start[k], self.len[k] = st, ln
+            self.c.start[k] = st.ctypes.data
+            self.c.len[k] = ln.ctypes.data
+
+    def _append_entries(self, arr):
+        """Append entries behind the last used one (the buffer keeps headroom; it moves only when that runs out)."""
+        need = self.n_ent + len(arr)
+        if need > len(self.ent):
+            ent = np.zeros(max(need, int(len(self.ent) * 1.25) + 4096), dtype=OENTRY)
+            ent[: self.n_ent] = self.ent[: self.n_ent]
+            self.ent = ent
+            self.c.ent = _p(self.ent)
+        at = self.n_ent
+        self.ent[at:need] = arr
+        self.n_ent = need
+        return at
+
+    def update(self, oracle, root, up, children, dist, n_minor, lists4, mutations=None):
+        """Bring the tree up to date IN PLACE: new topology arrays (the tree may have grown) and, per kind, new lists for
+        a set of nodes -- (node ids, packed lists) as from the device, or {node: tuple list or None}.  The new entries
+        are appended to the entry buffer and only those nodes' start/len are rewritten; every other list stays where it
+        is.  `mutations` (per node, or None) replaces the MAT mutations when given."""
+        u = oracle.u
+        up = np.ascontiguousarray(up, dtype=np.int32)
+        n = len(up)
+        children = np.asarray(children)
+        self.up = up
+        self.c0 = np.ascontiguousarray(children[:, 0], dtype=np.int32)
+        self.c1 = np.ascontiguousarray(children[:, 1], dtype=np.int32)
+        self.dist = np.ascontiguousarray(dist, dtype=np.float64)
+        self.nMinor = np.ascontiguousarray(n_minor, dtype=np.int32)
+        self._grow_nodes(n)
+        for kind in range(4):
+            item = lists4[kind]
+            if item is None:
+                continue
+            if isinstance(item, tuple):
+                nodes_k, pk = item
+                nodes_k = np.asarray(nodes_k, dtype=np.int64)
+                if len(nodes_k) == 0:
+                    continue
+                arr, off = packed_to_entries(pk, u)
+                at = self._append_entries(arr)
+                self.start[kind][nodes_k] = at + off[:-1]
+                self.len[kind][nodes_k] = np.diff(off)
+            else:
+                for v, gl in item.items():
+                    if gl:
+                        arr = to_entries([tuple(e) for e in gl], u)
+                        self.start[kind][v] = self._append_entries(arr)
+                        self.len[kind][v] = len(arr)
+                    else:
+                        self.len[kind][v] = 0
+        if mutations is not None:
+            off = np.zeros(n + 1, dtype=np.int64)
+            flat = []
+            for v in range(n):
+                flat.extend(mutations[v])
+                off[v + 1] = len(flat)
+            self.mut3 = np.ascontiguousarray(np.asarray(flat if flat else [[0, 0, 0]], dtype=np.int32).reshape(-1, 3))
+            self.mutOff = off
+        elif len(self.mutOff) < n + 1:                              # new nodes carry no mutations
+            off = np.full(n + 1, self.mutOff[-1], dtype=np.int64)
+            off[: len(self.mutOff)] = self.mutOff
+            self.mutOff = off
+        t = self.c
+        t.n, t.root = n, int(root)
+        t.up, t.c0, t.c1, t.dist, t.nMinor = _p(self.up), _p(self.c0), _p(self.c1), _p(self.dist), _p(self.nMinor)
+        t.mut3, t.mutOff = _p(self.mut3), _p(self.mutOff)
+        self.n = n
+        return self
 
 
 class Oracle:
@@ -438,6 +539,29 @@ class Oracle:
         else:
             self.lib.omo_appendProbNode_batch(C.byref(self.m), _p(allent), _p(off), n, _p(pl), _p(cl), _p(tip), _p(bl), _p(out))
         return out
+
+    # ---- sample placement -------------------------------------------------------------------------
+    def find_best_parent_for_new_sample(self, tree, query, *, oneMutBLen, effectivelyNon0BLen, thresholdLogLK,
+                                        thresholdLogLKoptimization, thresholdLogLKconsecutivePlacement, allowedFails,
+                                        strictStopRules, onlyFindIdentical=False, arena_mb=64, arena=None):
+        """findBestParentForNewSample(tree, root, query, ..., computePlacementSupportOnly=False), M:7912-8292.
+        Returns (status, bestNode, bestScore, branch lengths or None, bestDiffs, nAppend); status 0 placed, 1 minor
+        sequence (the tree is not modified)."""
+        q = query if isinstance(query, np.ndarray) else to_entries([tuple(e) for e in query], self.u)
+        pp = OPlaceParamsC(int(bool(strictStopRules)), int(allowedFails), int(bool(onlyFindIdentical)), oneMutBLen,
+                           thresholdLogLK, thresholdLogLKoptimization, thresholdLogLKconsecutivePlacement,
+                           effectivelyNon0BLen)
+        if arena is None:
+            arena = np.empty(arena_mb << 20, dtype=np.uint8)
+        dbuf = np.zeros(len(q) + 2 * len(tree.mut3) + 8, dtype=OENTRY)     # (passing MAT branches adds entries)
+        r = OPlaceResultC()
+        r.diffs, r.diffsCap = dbuf.ctypes.data, len(dbuf)
+        rc = self.lib.omo_findBestParentForNewSample(C.byref(self.m), C.byref(tree.c), C.byref(pp), _p(q), len(q), C.byref(r),
+                                                     _p(arena), C.c_size_t(arena.nbytes))
+        if rc != 0:
+            raise RuntimeError(f"omo_findBestParentForNewSample: {rc}")
+        blens = None if r.blenNone else [r.blen[0], r.blen[1], r.blen[2]]
+        return r.status, r.bestNode, r.bestScore, blens, from_entries(dbuf, r.diffsN, self.u), r.nAppend
 
     # ---- SPR search -----------------------------------------------------------------------------
     def spr_worker(self, tree, nodes, *, strict, allowedFails, thresholdLogLKtopology, thresholdTopologyPlacement,

@@ -46,8 +46,8 @@ def build_bench_tree(samples, model, arena_gb):
     return data, dev, mirror, ref_idx, root_freqs, mkw, tip_kw
 
 
-def oracle_tree(dev, ref_idx, root_freqs, mkw, root, parent, children, dist, lower, up_right, up_left, tot_up):
-    """The whole tree, lists and all, downloaded into the oracle's layout."""
+def oracle_tree(dev, ref_idx, root_freqs, mkw, root, parent, children, dist, lower, up_right, up_left, tot_up, headroom=0):
+    """The whole tree, lists and all, downloaded into the oracle's layout (``headroom`` entries of room for OracleTree.update)."""
     from oracle.oracle_py import Oracle, OracleTree
     orc = Oracle(ref_idx, root_freqs)
     orc.set_model(**mkw)
@@ -57,7 +57,8 @@ def oracle_tree(dev, ref_idx, root_freqs, mkw, root, parent, children, dist, low
         have = have[np.argsort(ids[have], kind="stable")]
         lists4.append((have, dev.download_packed(ids[have])))
     n = len(parent)
-    return orc, OracleTree(orc, int(root), np.asarray(parent, dtype=np.int32), np.asarray(children), dist, None, np.zeros(n, dtype=np.int32), lists4)
+    return orc, OracleTree(orc, int(root), np.asarray(parent, dtype=np.int32), np.asarray(children), dist, None, np.zeros(n, dtype=np.int32), lists4,
+                           headroom=headroom)
 
 
 def check_sample_against_oracle(orc, otree, nodes, gpu, sel, kw, max_ties=3):
@@ -186,6 +187,10 @@ def test_config5_online_update_of_the_1M_tree(million):
     bench's stand-in for placeSampleOnTree, host code of the reference that is out of scope), checked as follows
     (MAPLE_TEST_CONFIG5_ADD=<n> runs a shorter loop while working on the library):
 
+    * every 500th sample: the search's decision against the oracle's own findBestParentForNewSample on the same sample and tree
+      (status, node and candidate count exact, score 1e-9 relative, lengths 1e-8; a different node only as an exact tie, at most
+      1 % of the checks) -- the oracle's copy of the tree downloaded once and brought up to date in place at every check with the
+      lists of the nodes touched since the check before;
     * every 500th sample: the search's score and the three branch lengths against the oracle's evaluation of the SAME placement
       (the reference's refinement, M:8109-8147: three estimateBranchLengthWithDerivative around three mergeVectors, one
       appendProbNode, the branch-length compensation), and the lists updatePartials wrote around the new nodes against the
@@ -225,9 +230,16 @@ def test_config5_online_update_of_the_1M_tree(million):
     depth, dstep = bench.tree_depths(m.root, c0, c1, n0, cap)
     n = n0
     dev.upload_tree(m.root, up[:n], c0[:n], c1[:n], dist[:n], tip[:n], lower[:n], up_right[:n], up_left[:n], tot_up[:n], mut[:n])
-    from oracle.oracle_py import Oracle
-    orc = Oracle(ref_idx, root_freqs)
-    orc.set_model(**mkw)
+    t_dl = time.time()
+    # room for the lists the checks append: a placement touches ~7 nodes (4 lists each) of the mean list length of the tree.
+    # (The room is zero pages until written: what is resident grows with what the checks really append, reported below.)
+    ast = dev.stats()
+    mean_len = ast["n_entries"] / max(1, ast["n_lists"])
+    orc, otree = oracle_tree(dev, ref_idx, root_freqs, mkw, m.root, up[:n], np.stack([c0[:n], c1[:n]], axis=1), dist[:n], lower[:n],
+                             up_right[:n], up_left[:n], tot_up[:n], headroom=int(n_add * 7 * 4 * mean_len))
+    t_dl = time.time() - t_dl
+    o_room, o_ent0 = len(otree.ent) - otree.n_ent, otree.n_ent
+    since, o_checks, o_ties, o_time = [], 0, 0, 0.0
     touched_all = []
     placed = checked = 0
     t_loop = time.time()
@@ -248,11 +260,34 @@ def test_config5_online_update_of_the_1M_tree(million):
         out = dev.placement_search_batch(np.asarray([qid], dtype=np.int32), **pkw)
         dev.release(mark)
         b = int(out["bestNode"][0])
+        check = (k % every == 0)
+        if check:
+            # the oracle's own search on the same sample and the tree as it is now (its copy brought up to date in place first)
+            t_o = time.time()
+            tn = np.unique(np.concatenate(since)) if since else np.zeros(0, dtype=np.int64)
+            since = []
+            lists4 = []
+            for col in (lower, up_right, up_left, tot_up):
+                have = tn[col[tn] >= 0]
+                lists4.append((have, dev.download_packed(col[have])))
+            otree.update(orc, int(m.root), up[:n], np.stack([c0[:n], c1[:n]], axis=1), dist[:n], np.zeros(n, dtype=np.int32), lists4)
+            ost, onode, oscore, oblen, _, onapp = orc.find_best_parent_for_new_sample(otree, lst, allowedFails=5, strictStopRules=True, **pkw)
+            o_time += time.time() - t_o
+            o_checks += 1
+            gscore = float(out["bestScore"][0])
+            assert ost == int(out["status"][0]), (k, ost, out["status"][0])
+            if onode != b:                                                  # a tie: the same score to 1e-11
+                assert abs(oscore - gscore) <= 1e-11 * max(1.0, abs(oscore)), (k, onode, b, oscore, gscore)
+                o_ties += 1
+            else:
+                assert onapp == int(out["nAppend"][0]), (k, onapp, out["nAppend"][0])
+                assert abs(oscore - gscore) <= 1e-9 * max(1.0, abs(oscore)), (k, oscore, gscore)
+                if ost == 0:
+                    assert np.allclose(oblen, out["blen"][0], rtol=1e-8, atol=1e-15), (k, oblen, out["blen"][0])
         if out["status"][0] != 0 or up[b] < 0:
             continue
         top, bottom, app = (float(x) for x in out["blen"][0])
         g, p, s = int(up[b]), n, n + 1
-        check = (k % every == 0)
         if check:
             # the oracle's evaluation of this very placement on the lists of the tree as it is now (M:8109-8147)
             vu = int(up_right[g] if c0[g] == b else up_left[g])
@@ -285,6 +320,7 @@ def test_config5_online_update_of_the_1M_tree(million):
         dev.tree_patch(n, touched, up[touched], c0[touched], c1[touched], dist[touched], tip[touched], lower[touched],
                        up_right[touched], up_left[touched], tot_up[touched])
         touched_all.append(touched)
+        since.append(touched)
         placed += 1
         if check:
             # what updatePartials wrote around the new nodes, from the lists that are there now (M:5479-5815)
@@ -301,6 +337,14 @@ def test_config5_online_update_of_the_1M_tree(million):
                 assert len(lt) == len(want_t) and all(x[0] == y[0] and x[1] == y[1] for x, y in zip(lt, want_t)), k
             checked += 1
     loop_s = time.time() - t_loop
+    import resource
+    o_added = otree.n_ent - o_ent0
+    del otree
+    assert o_checks >= n_add // every and o_ties <= o_checks // 100, (o_checks, o_ties)
+    print(f"config 5: {o_checks} searches against the oracle's findBestParentForNewSample ({o_ties} ties); the oracle's tree "
+          f"({o_ent0 / 1e6:.0f} M entries) downloaded in {t_dl:.1f} s, {o_time / max(1, o_checks) * 1e3:.0f} ms per check (update in "
+          f"place + search); {o_added / 1e6:.1f} M entries appended of {o_room / 1e6:.1f} M of room ({64 * o_room / 2**30:.1f} GiB "
+          f"reserved); peak RSS {resource.getrusage(resource.RUSAGE_SELF).ru_maxrss / 2**20:.1f} GiB")
     ahead_stats = dev.placement_ahead_stats()
     assert placed > 0.95 * n_add and checked >= 0.85 * (n_add // every)
     assert ahead_stats["searches"] == n_add and ahead_stats["fallbacks"] <= 0.05 * n_add, ahead_stats

@@ -1009,3 +1009,350 @@ def test_serial_loop_with_rows_made_ahead_equals_the_plain_loop(mode):
     assert stats[4]["traversals_ahead_used"] == 0 and stats[4]["traversals_ahead_dropped"] == 0
     print("rows made ahead:", stats)
     dev.close()
+
+
+# ---- the announced serial loop at its edges ------------------------------------------------------------------------------
+# Each test below runs the serial placement loop (bench.serial_phase's stand-in tree edit) with its samples announced
+# (maple_placement_ahead) and without, on the same inputs and with the same interleaved calls, and requires the same result of
+# every search bit for bit; on a sample of the searches it also requires the C oracle's findBestParentForNewSample on the tree
+# as it is then (an OracleTree downloaded once and brought up to date in place with the nodes touched since the last check).
+
+def small_pkw(l_ref):
+    ll = math.log(l_ref)
+    return dict(oneMutBLen=1.0 / l_ref, effectivelyNon0BLen=1.0 / (10 * l_ref), thresholdLogLK=18.0 * ll,
+                thresholdLogLKoptimization=1.0 * ll, thresholdLogLKconsecutivePlacement=1.0)
+
+
+def serial_loop(dev, m, new_lists, pkw, ahead=0, hook=None, orc=None, oracle_every=0, stop=None):
+    """The serial placement loop on TreeMirror ``m`` (the edit of bench.serial_phase) with a hook before every search:
+    hook(k, st) may call the library between two searches and edit st["waiting"] (the announced samples not yet searched, in
+    order) -- it is called in the plain loop too.  Announced loops take ``ahead`` samples at a time; their lists are uploaded
+    before any per-search mark.  Returns the per-search results (status, node, score, lengths, nAppend), the steps at which the
+    root's lower list got a new id, and the oracle checks (k, oracle's answer, result).  ``stop``: search only that many."""
+    import bench
+    n_add = len(new_lists)
+    n0, cap = m.n_nodes, m.n_nodes + 2 * n_add
+
+    def grown(a, fill, dtype):
+        out = np.full(cap, fill, dtype=dtype)
+        out[:n0] = a
+        return out
+    up = grown(m.parent, -1, np.int32)
+    c0, c1 = grown(m.children[:, 0], -1, np.int32), grown(m.children[:, 1], -1, np.int32)
+    tip = grown(m.is_tip, 0, np.uint8)
+    dist = grown(m.dist, 0.0, np.float64)
+    mut = np.full(cap, -1, dtype=np.int32)
+    lower, up_right = grown(m.lower, -1, np.int32), grown(m.up_right, -1, np.int32)
+    up_left, tot_up = grown(m.up_left, -1, np.int32), grown(m.tot_up, -1, np.int32)
+    depth, dstep = bench.tree_depths(m.root, c0, c1, n0, cap)
+    n = n0
+    dev.upload_tree(m.root, up[:n], c0[:n], c1[:n], dist[:n], tip[:n], lower[:n], up_right[:n], up_left[:n], tot_up[:n], mut[:n])
+    st = dict(dev=dev, pkw=pkw, ahead=ahead, waiting=[], rest=[], new_lists=new_lists,
+              cols=dict(up=up, c0=c0, c1=c1, dist=dist, tip=tip, lower=lower, up_right=up_right, up_left=up_left, tot_up=tot_up),
+              extra_touched=[], n=n)
+    results, root_changes, checks = [], [], []
+    otree, since = None, []
+    if orc is not None:
+        from oracle.oracle_py import OracleTree
+        lists4 = []
+        for ids in (lower[:n], up_right[:n], up_left[:n], tot_up[:n]):
+            have = np.nonzero(ids >= 0)[0]
+            lists4.append((have, dev.download_packed(ids[have])))
+        otree = OracleTree(orc, int(m.root), up[:n].copy(), np.stack([c0[:n], c1[:n]], axis=1), dist[:n].copy(), None,
+                           np.zeros(n, dtype=np.int32), lists4)
+    for k in range(n_add if stop is None else stop):
+        st["k"], st["n"] = k, n
+        dev.placement_prepare(**pkw)
+        if ahead > 0 and not st["waiting"]:
+            if not st["rest"]:
+                st["rest"] = [int(x) for x in dev.upload(new_lists[k: k + ahead])]
+            got = dev.placement_ahead(np.asarray(st["rest"], dtype=np.int32), **pkw)
+            got = got if got > 0 else len(st["rest"])
+            st["waiting"], st["rest"] = st["rest"][:got], st["rest"][got:]
+        if hook is not None:
+            hook(k, st)
+        if ahead > 0:
+            qid = st["waiting"].pop(0)
+        else:
+            qid = int(dev.upload([new_lists[k]])[0])
+        mark = dev.mark()
+        out = dev.placement_search_batch(np.asarray([qid], dtype=np.int32), **pkw)
+        dev.release(mark)
+        b = int(out["bestNode"][0])
+        res = (int(out["status"][0]), b, float(out["bestScore"][0]), tuple(float(x) for x in out["blen"][0]), int(out["nAppend"][0]))
+        results.append(res)
+        if otree is not None and k % oracle_every == 0:
+            touched = np.unique(np.concatenate([np.asarray(x, dtype=np.int64) for x in since + st["extra_touched"]] or [np.zeros(0, np.int64)]))
+            st["extra_touched"] = []
+            since = []
+            lists4 = []
+            for col in (lower, up_right, up_left, tot_up):
+                ids = col[touched]
+                have = touched[ids >= 0]
+                lists4.append((have, dev.download_packed(col[have])))
+            otree.update(orc, int(m.root), up[:n].copy(), np.stack([c0[:n], c1[:n]], axis=1), dist[:n].copy(), np.zeros(n, dtype=np.int32), lists4)
+            o = orc.find_best_parent_for_new_sample(otree, new_lists[k], allowedFails=5, strictStopRules=True, **pkw)
+            checks.append((k, o, res))
+        if res[0] != 0 or up[b] < 0:
+            continue
+        top, bottom, app = res[3]
+        g, p, s = int(up[b]), n, n + 1
+        depth, dstep = bench.place_depths(depth, dstep, g, p, b, s, m.root, c0, c1, n)
+        if c0[g] == b:
+            c0[g] = p
+        else:
+            c1[g] = p
+        up[p], c0[p], c1[p], dist[p], tip[p] = g, b, s, top, 0
+        up[b], dist[b] = p, bottom
+        up[s], dist[s], tip[s], lower[s] = p, app, 1, qid
+        n += 2
+        root_lower = int(lower[m.root])
+        dev.update_partials(m.root, up[:n], c0[:n], c1[:n], tip[:n], mut[:n], depth[:n], dist[:n], lower[:n], up_right[:n],
+                            up_left[:n], tot_up[:n], [b, s, p])
+        if int(lower[m.root]) != root_lower:
+            root_changes.append(k)
+        touched = np.unique(np.concatenate([dev.update_partials_touched(), [g, b, p, s]])).astype(np.int32)
+        dev.tree_patch(n, touched, up[touched], c0[touched], c1[touched], dist[touched], tip[touched], lower[touched],
+                       up_right[touched], up_left[touched], tot_up[touched])
+        since.append(touched)
+    st["n"] = n
+    return dict(results=results, root_changes=root_changes, checks=checks, st=st)
+
+
+def check_against_oracle(checks, min_checks):
+    """The oracle's answer on the sampled searches: status, node and nAppend exact, score 1e-9 relative, lengths 1e-8; a different
+    node only as a tie (both scores within 1e-11 relative), at most one in a hundred checks."""
+    ties = 0
+    for k, (ost, onode, oscore, oblen, _, onapp), (gst, gnode, gscore, gblen, gnapp) in checks:
+        assert ost == gst, (k, ost, gst)
+        if onode != gnode:
+            assert abs(oscore - gscore) <= 1e-11 * max(1.0, abs(oscore)), (k, onode, gnode, oscore, gscore)
+            ties += 1
+            continue
+        assert onapp == gnapp, (k, onapp, gnapp)
+        assert abs(oscore - gscore) <= 1e-9 * max(1.0, abs(oscore)), (k, oscore, gscore)
+        if ost == 0:
+            assert np.allclose(oblen, gblen, rtol=1e-8, atol=1e-15), (k, oblen, gblen)
+    assert len(checks) >= min_checks and ties <= len(checks) // 100, (len(checks), ties)
+    return ties
+
+
+def small_world(mode, n_tips, seed, n_add, near_root=0):
+    """A small tree (n_tips tips) and n_add new samples: perturbed copies of random tips, every 25th an exact copy (a minor
+    sequence), and -- near_root > 0 -- copies of the near_root tips closest to the root."""
+    from maple_amd.host import tip_genome_list
+    from maple_amd.synth import perturb_diffs
+    data, dev, orc, m = build(n_tips, mode, seed=seed)
+    kw = world_model_kwargs(mode, dev.lRef, seed)
+    tip_kw = dict(error_rates=kw["errorRates"]) if mode == "siteerr" else {}
+    prng = np.random.default_rng(seed + 7)
+    src = list(prng.choice(len(data.diffs), size=n_add, replace=True))
+    if near_root:
+        node_of = {int(v): i for i, v in enumerate(data.tip_node)}
+        d = np.full(m.n_nodes, -1)
+        d[m.root] = 0
+        order = [m.root]
+        for v in order:
+            for c in m.children[v]:
+                if c >= 0:
+                    d[c] = d[v] + 1
+                    order.append(int(c))
+        shallow = sorted((int(d[v]), v) for v in node_of)[:near_root]
+        for j, (_, v) in enumerate(shallow):
+            src[(3 * j + 1) % n_add] = node_of[v]
+    new_lists = []
+    for k, i in enumerate(src):
+        dl = data.diffs[int(i)] if k % 25 == 0 else perturb_diffs(data.diffs[int(i)], data.ref, prng)
+        new_lists.append(tip_genome_list(dl, dev.ref_idx, **tip_kw))
+    return data, dev, orc, m, new_lists
+
+
+def test_announced_loop_root_column_under_full_row_fallback():
+    """Finding 1: when the traversal asks for a branch the expansion did not reach, the sample's row is scored in full once more --
+    and the root's column of that row must stay the CURRENT root vector's score.  A 300-tip tree, the expansion cut short
+    (no_ahead_expansion=2: most searches fall back), copies of the tips closest to the root among the samples.  The placements
+    of the stand-in edit do not give the root a new lower list on this tree (updatePartials stops below it), so the root's list
+    is rewritten in place every 5th step with the list of the sample searched next, which then goes to the root: a stale root
+    column gives another result."""
+    data, dev, orc, m, new_lists = small_world("ratevar", 300, 31, 120, near_root=8)
+    pkw = small_pkw(dev.lRef)
+    saved = []
+
+    def new_root_list(k, st):
+        # (the placements do not give the root a new lower list on this tree: every 5th step it is rewritten in place --
+        # maple_lists_update, then maple_tree_patch of the root -- with the list of the sample searched next, which then scores
+        # best at the root; a stale root column gives another result)
+        if k % 5:
+            return
+        cols, d = st["cols"], st["dev"]
+        rid = int(cols["lower"][m.root])
+        saved.append((rid, d.download([rid])[0]))
+        d.update_lists([rid], [st["new_lists"][k]])
+        v = np.asarray([m.root], dtype=np.int32)
+        d.tree_patch(st["n"], v, *(cols[c][v] for c in ("up", "c0", "c1", "dist", "tip", "lower", "up_right", "up_left", "tot_up")))
+        st["extra_touched"].append(v)
+        st.setdefault("root_rewrites", []).append(k)
+
+    runs, stats = [], []
+    for ahead, expansion in ((0, 0), (40, 2)):
+        mark = dev.mark()
+        dev.set_tuning(no_ahead_expansion=expansion)
+        before = dev.placement_ahead_stats()
+        runs.append(serial_loop(dev, m, new_lists, pkw, ahead=ahead, hook=new_root_list, orc=orc if ahead else None, oracle_every=6))
+        after = dev.placement_ahead_stats()
+        stats.append({k: after[k] - before[k] for k in after})
+        for rid, lst in reversed(saved):                                   # (the tree's own lists back for the next loop)
+            dev.update_lists([rid], [lst])
+        saved.clear()
+        dev.release(mark)
+    dev.set_tuning()
+    plain, ahead = runs
+    assert plain["results"] == ahead["results"]
+    assert plain["root_changes"] == ahead["root_changes"]
+    rewrites = ahead["st"]["root_rewrites"]
+    assert len(rewrites) >= 20, rewrites
+    assert sum(ahead["results"][k][1] == m.root for k in rewrites) >= 10       # (the rewritten root list did change the results)
+    assert stats[1]["searches"] == len(new_lists) and stats[1]["fallbacks"] > 0.5 * len(new_lists), stats[1]
+    check_against_oracle(ahead["checks"], 15)
+    next_to_root = sum(1 for r in ahead["results"] if r[0] == 0 and r[1] in (int(m.children[m.root][0]), int(m.children[m.root][1])))
+    print(f"root lower list renewed at {len(ahead['root_changes'])} of {len(new_lists)} steps by the placements, rewritten at "
+          f"{len(rewrites)}; {next_to_root} placed on a child "
+          f"branch of the root; {stats[1]}")
+    dev.close()
+
+
+def test_announced_loop_sees_a_list_rewritten_in_place():
+    """Finding 2: maple_lists_update keeps a list's id; the node is then passed to maple_tree_patch with unchanged ids.  Between
+    two announced searches, the mid-branch (tot_up) list of the branch the next sample goes to (found by a plain loop without
+    the rewrite) gets the contents of a far branch's mid-branch list: a tip's in the other subtree of the root.  The branch then
+    scores far worse for that sample and the search returns another node; a row left stale keeps the old winner.  The rewrite
+    comes right after the second batch is announced (no column of that batch is dirty yet), and the rows hold every branch
+    (no_ahead_expansion=1: no search falls back to scoring its row in full, which would hide a stale column).  The plain loop
+    gets the same rewrite; every search must equal it, and the oracle on the rewritten tree."""
+    data, dev, orc, m, new_lists = small_world("unrest", 300, 37, 40)
+    pkw = small_pkw(dev.lRef)
+    at = 16                                                              # (the first sample of the second batch of 16)
+    done, winner = [], []
+
+    def rewrite(k, st):
+        if k != at:
+            return
+        cols, d = st["cols"], st["dev"]
+        w = winner[0]
+        assert w != m.root
+        side = w
+        while cols["up"][side] != m.root:                                  # (the child of the root above the winner)
+            side = int(cols["up"][side])
+        other = int(cols["c1"][m.root] if cols["c0"][m.root] == side else cols["c0"][m.root])
+        far, stack = [], [other]                                           # (tips below the other child with a mid-branch list)
+        while stack:
+            v = stack.pop()
+            if cols["c0"][v] >= 0:
+                stack += [int(cols["c0"][v]), int(cols["c1"][v])]
+            elif cols["dist"][v] > pkw["effectivelyNon0BLen"] and cols["tot_up"][v] >= 0:
+                far.append(v)
+        assert far
+        tid = int(cols["tot_up"][w])
+        done.append((w, tid, d.download([tid])[0]))
+        d.update_lists([tid], d.download([int(cols["tot_up"][far[0]])]))
+        v = np.asarray([w], dtype=np.int32)
+        d.tree_patch(st["n"], v, *(cols[c][v] for c in ("up", "c0", "c1", "dist", "tip", "lower", "up_right", "up_left", "tot_up")))
+        st["extra_touched"].append(v)
+
+    mark = dev.mark()
+    untouched = serial_loop(dev, m, new_lists, pkw)                      # (the plain loop without the rewrite)
+    dev.release(mark)
+    assert untouched["results"][at][0] == 0
+    winner.append(untouched["results"][at][1])
+    runs, stats = [], []
+    for ahead in (0, 16):
+        mark = dev.mark()
+        dev.set_tuning(no_ahead_expansion=1)
+        before = dev.placement_ahead_stats()
+        runs.append(serial_loop(dev, m, new_lists, pkw, ahead=ahead, hook=rewrite, orc=orc if ahead else None, oracle_every=1))
+        after = dev.placement_ahead_stats()
+        dev.set_tuning()
+        stats.append({k: after[k] - before[k] for k in after})
+        _, tid, original = done[-1]
+        dev.update_lists([tid], [original])                              # (the list as it was, in case it is the tree's own)
+        dev.release(mark)
+    plain, ahead = runs
+    print(f"winner {winner[0]} rewritten: the search after it {untouched['results'][at]} -> {plain['results'][at]}")
+    assert plain["results"][at][1] != untouched["results"][at][1]      # (the rewrite moves the decision: a stale row would not)
+    assert plain["results"] == ahead["results"]
+    assert stats[1]["searches"] == len(new_lists) and stats[1]["fallbacks"] == 0, stats[1]
+    check_against_oracle(ahead["checks"], 30)
+    dev.close()
+
+
+def test_announced_loop_interleaved_calls_mid_batch():
+    """Calls between two announced searches, each followed by the rest of the announced samples: a search of a sample that was
+    not announced; placement_prepare with another effectivelyNon0BLen and back; a release of a mark below announced samples'
+    lists (they are uploaded and announced again); set_model with the same model.  maple_hip.h says which of these drop the
+    rows; the results must be those of the plain loop with the same calls in between."""
+    mode = "ratevar"
+    data, dev, orc, m, new_lists = small_world(mode, 400, 41, 72)
+    pkw = small_pkw(dev.lRef)
+    kw = world_model_kwargs(mode, dev.lRef, 41)
+    stranger = new_lists[5]
+    seen = {}
+
+    def interleave(k, st):
+        d = st["dev"]
+        if k == 3:                                                          # a search of a sample nobody announced
+            mk = d.mark()
+            qid = d.upload([stranger])
+            seen.setdefault(st["ahead"], []).append(d.placement_search_batch(qid, **st["pkw"]))
+            d.release(mk)
+        elif k == 9:                                                        # other parameters of the tables, then these again
+            d.placement_prepare(**dict(st["pkw"], effectivelyNon0BLen=st["pkw"]["effectivelyNon0BLen"] * 50))
+            d.placement_prepare(**st["pkw"])
+        elif k == 20:                                                       # the waiting samples' lists released, then again
+            if st["ahead"]:
+                mk = d.mark()
+                ids = [int(x) for x in d.upload([st["new_lists"][k + j] for j in range(len(st["waiting"]))])]
+                assert d.placement_ahead(np.asarray(ids, dtype=np.int32), **st["pkw"]) > 0
+                d.release(mk)
+                ids = [int(x) for x in d.upload([st["new_lists"][k + j] for j in range(len(ids))])]
+                got = d.placement_ahead(np.asarray(ids, dtype=np.int32), **st["pkw"])
+                st["waiting"] = ids[:got] if got > 0 else ids
+        elif k == 30:                                                       # the same model again
+            d.set_model(**kw)
+
+    runs, stats = [], []
+    for ahead in (0, 24):
+        mark = dev.mark()
+        before = dev.placement_ahead_stats()
+        runs.append(serial_loop(dev, m, new_lists, pkw, ahead=ahead, hook=interleave, orc=orc if ahead else None, oracle_every=4))
+        after = dev.placement_ahead_stats()
+        stats.append({k: after[k] - before[k] for k in after})
+        dev.release(mark)
+    plain, ahead = runs
+    assert plain["results"] == ahead["results"]
+    for k in ("status", "bestNode", "bestScore", "blen", "nAppend"):
+        assert np.array_equal(seen[0][0][k], seen[24][0][k]), k
+    assert stats[1]["searches"] >= len(new_lists) // 2, stats[1]
+    check_against_oracle(ahead["checks"], 15)
+    print("interleaved:", stats[1])
+    dev.close()
+
+
+def test_announced_loop_closed_mid_batch_then_a_fresh_context():
+    """A context closed halfway through an announced batch, with the traversal of the next sample made ahead on (its thread is
+    joined before anything is freed); a fresh context then runs the whole loop: the plain loop's results."""
+    from maple_amd.runtime import Device
+    data, dev, orc, m, new_lists = small_world("ratevar", 300, 43, 48)
+    pkw = small_pkw(dev.lRef)
+    mark = dev.mark()
+    plain = serial_loop(dev, m, new_lists, pkw, ahead=0)
+    dev.release(mark)
+    half = serial_loop(dev, m, new_lists, pkw, ahead=48, stop=24)        # (48 announced, 24 searched)
+    assert half["results"] == plain["results"][:24]
+    assert dev.placement_ahead_stats()["traversals_ahead_used"] > 0
+    dev.close()
+    data2, dev2, orc2, m2, lists2 = small_world("ratevar", 300, 43, 48)
+    assert all(a == b for a, b in zip(lists2, new_lists))
+    whole = serial_loop(dev2, m2, lists2, pkw, ahead=48)
+    assert whole["results"] == plain["results"]
+    assert dev2.placement_ahead_stats()["searches"] == len(new_lists)
+    dev2.close()

@@ -843,6 +843,85 @@ def test_online_sample_additions_through_tree_patch(name):
     dev.close()
 
 
+def _has_mat(f):
+    """Does the recorded online sequence ever have MAT local references (mutations on a branch)?"""
+    topos = [f["online_start"]] + [r["after"] for r in f["online"]]
+    return any(any(m for m in (t.get("mutations") or [])) for t in topos)
+
+
+def test_an_e2e_fixture_without_mat_references():
+    """The announced loop below makes rows only on trees without MAT references: at least one fixture must be one."""
+    assert any(not _has_mat(json.load(gzip.open(os.path.join(GOLDEN, f"e2e_{n}.json.gz"), "rt"))) for n in E2E_NAMES)
+
+
+@pytest.mark.parametrize("chunk", [30, 7])
+@pytest.mark.parametrize("name", E2E_NAMES)
+def test_announced_online_sample_additions_match_reference(name, chunk):
+    """The sequence of test_online_sample_additions_through_tree_patch with its samples announced (maple_placement_ahead:
+    `chunk` at a time, so that with 7 the batch boundaries fall inside the sequence): every search must still return the
+    reference's own recorded node, score and branch lengths.  The queries are uploaded before any per-step mark, so the
+    per-search release leaves them.  On a fixture without MAT references every search takes its row; where the tree has MAT
+    references nothing is taken (nTaken 0) and the results are the same."""
+    from maple_amd.tree_host import update_genome_lists
+    f, dev = _e2e_env(name)
+    ctx = f["context"]
+    dev.set_model(**model_args(f["model"]))
+    tree = _tree_from_topology(dev, f["online_start"], f["tips"])
+    pkw = dict(oneMutBLen=ctx["oneMutBLen"], effectivelyNon0BLen=ctx["effectivelyNon0BLen"], thresholdLogLK=ctx["thresholdLogLK"],
+               thresholdLogLKoptimization=ctx["thresholdLogLKoptimization"],
+               thresholdLogLKconsecutivePlacement=ctx["thresholdLogLKconsecutivePlacement"], allowedFails=ctx["allowedFails"],
+               strictStopRules=ctx["strictStopRules"])
+    tree.upload_topology(dev)
+    recs = f["online"]
+    qids = [int(x) for x in dev.upload([tup(r["query"]) for r in recs])]
+    s0 = dev.placement_ahead_stats()
+    waiting, n_taken, n_announced_on_mat = [], 0, 0
+    for k, rec in enumerate(recs):
+        tree.sync(dev)
+        dev.placement_prepare(**pkw)
+        if not waiting:
+            batch = qids[k: k + chunk]
+            got = dev.placement_ahead(np.asarray(batch, dtype=np.int32), **pkw)
+            if any(tree.mutations):
+                assert got == 0, (k, got)                             # (a tree with MAT references: the call changes nothing)
+                n_announced_on_mat += 1
+            n_taken += got
+            waiting = batch[:got] if got > 0 else batch
+        qid = waiting.pop(0)
+        assert qid == qids[k]
+        mark = dev.mark()
+        out = dev.placement_search_batch(np.asarray([qid], dtype=np.int32), **pkw)
+        dev.release(mark)
+        want = rec["ret"]
+        assert out["status"][0] >= 0
+        assert int(out["bestNode"][0]) == want["bestNode"], (k, out["bestNode"][0], want["bestNode"])
+        assert close(float(out["bestScore"][0]), want["bestScore"], 1e-8), (k, out["bestScore"][0], want["bestScore"])
+        if want["bestBranchLengths"] is None:
+            assert out["status"][0] == 1
+        else:
+            assert all(close(float(g), w, 1e-6, 1e-15) for g, w in zip(out["blen"][0], want["bestBranchLengths"])), (k, out["blen"][0], want)
+        after = rec["after"]
+        changed = tree.apply_topology(after["root"], after["up"], after["children"], after["dist"], after["nMinor"],
+                                      after.get("mutations"), dev)
+        for v, lst in rec["new_tips"].items():
+            tree.id_lower[int(v)] = dev.upload([tup(lst)])[0]
+            if int(v) not in changed:
+                changed.append(int(v))
+        if changed:
+            update_genome_lists(dev, tree, changed)
+    s1 = dev.placement_ahead_stats()
+    used = s1["searches"] - s0["searches"]
+    print(f"{name} (announced {chunk} at a time): {n_taken} taken, {used} searches on rows, "
+          f"{s1['fallbacks'] - s0['fallbacks']} scored in full, {s1['traversals_ahead_used'] - s0['traversals_ahead_used']} traversals "
+          f"made ahead used")
+    if not _has_mat(f):
+        assert n_taken == len(recs) and used == len(recs), (n_taken, used)
+    else:
+        assert used <= n_taken
+        assert chunk >= len(recs) or n_announced_on_mat > 0       # (announced at least once on a tree with MAT references)
+    dev.close()
+
+
 @pytest.mark.parametrize("name", E2E_NAMES)
 def test_online_sample_additions(name):
     """BASELINE configs[4] in small (online update of a frozen tree): new samples are added one after the other -- placement
