@@ -14,6 +14,44 @@
 #include <string.h>
 
 #define U_(m) ((m)->usingErrorRate)
+
+/* Branch counters for the coverage gate of tests/test_list_edges_coverage.py: compiled in only with -DOMO_BRANCH_COUNTS (the
+ * default build, the one the golden tests pin, has none).  Each counts one rarely taken branch of the operators below. */
+#ifdef OMO_BRANCH_COUNTS
+enum {
+    BC_APPEND_R_D1_O,           /* appendProbNode: R with d0 and d1 against an O vector at <= 0.02, M:6611-6633 */
+    BC_APPEND_NUC_D1_O,         /* appendProbNode: nucleotide with d0 and d1 against an O vector at <= 0.02, M:6744-6761 */
+    BC_APPEND_CARRY3,           /* appendProbNode: a third carry-over within one call, M:6772-6783 */
+    BC_MERGE_CARRY,             /* mergeVectors(returnLK): the running factor carried over into the log, M:4830-4839 */
+    BC_MERGE_UNDERFLOW,         /* mergeVectors(returnLK): the running factor below DBL_MIN (the reference raises, M:4831-4836) */
+    BC_MERGE_UPDOWN_N_ERR_D0,   /* mergeVectors(isUpDown), error model: N against an entry that carries d0, M:4517-4518 */
+    BC_MERGE_UPDOWN_N_O_ZERO,   /* mergeVectors(isUpDown): N against an O vector of total length 0, M:4560-4561 */
+    BC_BLEN_NONE_R_D1,          /* estimateBranchLengthWithDerivative: None, R with d1 against a zero rate, M:5171-5172 */
+    BC_BLEN_NONE_R_FLAG,        /* ... None, tail-less R against a flagged nucleotide over a zero rate, M:5178-5179 */
+    BC_BLEN_NONE_NUC_D1,        /* ... None, nucleotide with d1 against a zero rate, M:5241-5242 */
+    BC_BLEN_EARLY_TENTH,        /* ... the early return of 0.1 when vDown > c1 + sens and tDown >= 0.1, M:5341-5342 */
+    BC_EVALPLACE_TOP_FALLBACK,  /* evaluatePlacement: the top merge returned None, bestTop = defaultBLen * 0.1, M:6798-6802 */
+    BC_N
+};
+static const char *const omo_bc_names[BC_N] = {
+    "append_R_d1_O", "append_nuc_d1_O", "append_carry3", "merge_carry", "merge_underflow", "merge_updown_N_err_d0",
+    "merge_updown_N_O_zero", "blen_none_R_d1", "blen_none_R_flag", "blen_none_nuc_d1", "blen_early_tenth",
+    "evalplace_top_fallback"};
+static long long omo_bc[BC_N];
+#define BC(k) __atomic_fetch_add(&omo_bc[k], 1, __ATOMIC_RELAXED)
+/* copies up to n counters into out (and their names into names, if given), zeroes them when reset; returns how many exist */
+int omo_branch_counts(long long *out, const char **names, int n, int reset)
+{
+    for (int k = 0; k < BC_N && k < n; k++) {
+        if (out) out[k] = __atomic_load_n(&omo_bc[k], __ATOMIC_RELAXED);
+        if (names) names[k] = omo_bc_names[k];
+        if (reset) __atomic_store_n(&omo_bc[k], 0, __ATOMIC_RELAXED);
+    }
+    return BC_N;
+}
+#else
+#define BC(k) ((void)0)
+#endif
 static inline int imin(int a, int b) { return a < b ? a : b; }
 static inline double pymin(double a, double b) { return (b < a) ? b : a; } /* Python min(a,b) */
 
@@ -208,6 +246,9 @@ int omo_appendProbNode(const OModel *m, const OEntry *P, int nP, const OEntry *C
     double Lkcost = bLen * m->globalTotRate;                         /* M:6541 */
     double M[16], tot2[4], tot3[4];
     double errorRate = m->errorRate;
+#ifdef OMO_BRANCH_COUNTS
+    int nCarry = 0;
+#endif
     (void)nP; (void)nC;
     memcpy(M, m->Q, sizeof M);
     if (U && isTipC) Lkcost += m->totError;                          /* M:6542-6543 */
@@ -258,6 +299,7 @@ int omo_appendProbNode(const OModel *m, const OEntry *P, int nP, const OEntry *C
                         double tot;
                         if (e1->len == 4 + U) {
                             int flag1 = (U && e1->len > 2 && e1->flag);
+                            BC(BC_APPEND_R_D1_O);
                             tot = 0.0;
                             if (U && SS) errorRate = m->errorRates[pos];
                             omo_getPartialVec(m, 6, contribLength, M, 0.0, e2->vec, 0, 0, tot3);
@@ -361,6 +403,7 @@ int omo_appendProbNode(const OModel *m, const OEntry *P, int nP, const OEntry *C
                         if (e2->vec[i1] > 0.02) totalFactor *= e2->vec[i1];
                         else {
                             if (e1->len == 4 + U) {
+                                BC(BC_APPEND_NUC_D1_O);
                                 omo_getPartialVec(m, i1, e1->d0, M, errorRate, NULL, 0, flag1, tot2);
                                 omo_getPartialVec(m, 6, contribLength, M, errorRate, e2->vec, 0, 0, tot3);
                                 double tot = 0.0;
@@ -383,6 +426,9 @@ int omo_appendProbNode(const OModel *m, const OEntry *P, int nP, const OEntry *C
         }
         if (totalFactor <= m->minimumCarryOver) {                    /* M:6772-6783 */
             if (totalFactor < DBL_MIN) { *outLK = -INFINITY; return 0; }
+#ifdef OMO_BRANCH_COUNTS
+            if (++nCarry == 3) BC(BC_APPEND_CARRY3);
+#endif
             Lkcost += log(totalFactor);
             totalFactor = 1.0;
         }
@@ -428,7 +474,7 @@ int omo_mergeVectors(const OModel *m, const OEntry *pv1, int n1, double bLen1, i
                             if (bLen2 != 0.0 || fromTip2) out[no++] = mk(e2->type, newEl, 5, bLen2, 0.0, fromTip2);
                             else out[no++] = mk(e2->type, newEl, 2, 0, 0, 0);
                         } else if (e2->len == 3) return -3;          /* unreachable in the reference (M:4515-4516) */
-                        else out[no++] = mk(e2->type, newEl, 5, e2->d0 + bLen2, 0.0, e2->flag);
+                        else { BC(BC_MERGE_UPDOWN_N_ERR_D0); out[no++] = mk(e2->type, newEl, 5, e2->d0 + bLen2, 0.0, e2->flag); }
                     } else {
                         if (e2->len > 2) out[no++] = mk(e2->type, newEl, 4, e2->d0 + bLen2, 0.0, 0);
                         else if (bLen2 != 0.0) out[no++] = mk(e2->type, newEl, 4, bLen2, 0.0, 0);
@@ -454,7 +500,7 @@ int omo_mergeVectors(const OModel *m, const OEntry *pv1, int n1, double bLen1, i
                     double totBLen = bLen2;
                     if (e2->len > 3) totBLen += e2->d0;
                     if (totBLen != 0.0) omo_getPartialVec(m, 6, totBLen, M, 0, e2->vec, 0, 0, newVec);
-                    else memcpy(newVec, e2->vec, sizeof newVec);
+                    else { BC(BC_MERGE_UPDOWN_N_O_ZERO); memcpy(newVec, e2->vec, sizeof newVec); }
                     for (int i = 0; i < 4; i++) newVec[i] *= rf[i];
                     totSum = 0.0; for (int i = 0; i < 4; i++) totSum += newVec[i];
                     for (int i = 0; i < 4; i++) newVec[i] /= totSum;
@@ -643,7 +689,8 @@ int omo_mergeVectors(const OModel *m, const OEntry *pv1, int n1, double bLen1, i
             pos = newPos;
         }
         if (returnLK && totalFactor <= m->minimumCarryOver) {        /* M:4830-4839 */
-            if (totalFactor < DBL_MIN) return -2;
+            if (totalFactor < DBL_MIN) { BC(BC_MERGE_UNDERFLOW); return -2; }
+            BC(BC_MERGE_CARRY);
             cumulPartLk += log(totalFactor);
             totalFactor = 1.0;
         }
@@ -733,13 +780,13 @@ int omo_estimateBranchLength(const OModel *m, const OEntry *P, int nP, const OEn
                             if (flag1) coeff0 += rf[i2] * 0.33333 * errorRate;
                             coeff1 = rf[i1] * M[i1 * 4 + i2];
                             if (coeff1 != 0.0) coeff0 = coeff0 / coeff1;
-                            else none = 1;
+                            else { BC(BC_BLEN_NONE_R_D1); none = 1; }
                         } else {
                             coeff0 = contribLength;
                             if (flag2) {
                                 double q = M[e2->x * 4 + e2->type];
                                 if (q != 0.0) coeff0 += errorRate * 0.33333 / q;
-                                else none = 1;
+                                else { BC(BC_BLEN_NONE_R_FLAG); none = 1; }
                             }
                         }
                         if (!none) { if (coeff0 != 0.0) ais[nA++] = coeff0; else nZeros++; }
@@ -778,7 +825,7 @@ int omo_estimateBranchLength(const OModel *m, const OEntry *P, int nP, const OEn
                                 if (flag1) coeff0 += rf[i2] * 0.33333 * errorRate;
                                 coeff1 = rf[i1] * M[i1 * 4 + i2];
                                 if (coeff1 != 0.0) coeff0 = coeff0 / coeff1;
-                                else none = 1;
+                                else { BC(BC_BLEN_NONE_NUC_D1); none = 1; }
                             } else {
                                 coeff0 = contribLength;
                                 if (flag2) coeff0 += errorRate * 0.33333 / M[i1 * 4 + i2];
@@ -841,7 +888,7 @@ int omo_estimateBranchLength(const OModel *m, const OEntry *P, int nP, const OEn
     for (int i = 0; i < nA; i++) vUp += 1.0 / (ais[i] + tUp);
     if (vDown > c1 + sens || vUp < c1 - sens) {
         if (vUp < c1 - sens && tUp == 0.0) { *isFalse = 1; *tOut = 0.0; return 0; }
-        if (vDown > c1 + sens && tDown >= 0.1) { *tOut = 0.1; return 0; }
+        if (vDown > c1 + sens && tDown >= 0.1) { BC(BC_BLEN_EARLY_TENTH); *tOut = 0.1; return 0; }
     }
     while (tDown - tUp > sens) {
         double tMiddle = (tUp + tDown) / 2;
@@ -1032,6 +1079,7 @@ int omo_evaluatePlacement(const OModel *m, const OEntry *midTot, int nMid, const
     omo_estimateBranchLength(m, up, nUp, midLower, nL, 0, &bestTop, &f, scratch);
     nT = omo_mergeVectors(m, up, nUp, bestTop, 0, rem, nRem, bestApp, isRemovedTip, 0, 1, 0, 0, midTop, NULL);
     if (nT == -1) {
+        BC(BC_EVALPLACE_TOP_FALLBACK);
         bestTop = defaultBLen * 0.1;
         nT = omo_mergeVectors(m, up, nUp, bestTop, 0, rem, nRem, bestApp, isRemovedTip, 0, 1, 0, 0, midTop, NULL);
     }

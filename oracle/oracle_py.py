@@ -324,9 +324,11 @@ class Oracle:
     """The reference's functions, by name, evaluated by the C restatement."""
 
     def __init__(self, ref_idx, root_freqs, thresholdProb=1e-8, minBLenSensitivity=None,
-                 thresholdDiffForUpdate=1e-5, thresholdFoldChangeUpdate=1.01, defaultBLen=0.000033):
-        build()
-        self.lib = C.CDLL(LIB)
+                 thresholdDiffForUpdate=1e-5, thresholdFoldChangeUpdate=1.01, defaultBLen=0.000033, lib_path=None):
+        """lib_path: another build of the same sources (e.g. with -DOMO_BRANCH_COUNTS); default libmaple_oracle.so."""
+        if lib_path is None:
+            build()
+        self.lib = C.CDLL(lib_path or LIB)
         self.lib.omo_simplify.restype = C.c_int
         self.ref_idx = np.ascontiguousarray(ref_idx, dtype=np.uint8)
         self.lRef = len(self.ref_idx)
