@@ -190,7 +190,7 @@ int maple_shorten_batch(maple_ctx *ctx, int32_t n, const int32_t *list, int32_t 
 int maple_root_vector_batch(maple_ctx *ctx, int32_t n, const int32_t *list, const double *bLen,
                             const uint8_t *isFromTip, const int64_t *pathOff, const int32_t *pathMutLists,
                             int32_t *outList);
-/* updatePartials(tree, nodeList), M:5479-5815, for ANY number of simultaneous local changes (maple_amd/csrc/update_host.h).
+/* updatePartials(tree, nodeList), M:5479-5815, for ANY number of simultaneous local changes (maple_amd/csrc/update.hip).
  * The tree is the caller's own: n nodes as plain columns -- up / child0 / child1 (-1 = none), isTip (leaf without minor
  * sequences), mutList (mutation-list id of the branch above the node, -1 = none), depth (branches from the root), dist,
  * and the four list-id columns lower / upRight / upLeft / totUp (-1 = None).  changed[] = nodes whose lower list (already

@@ -1,8 +1,8 @@
 /* include/maple_hip_debug.h -- measurement aids and test hooks of libmaple_hip_debug.so.
  *
  * NOT part of the operator boundary (include/maple_hip.h): the product library libmaple_hip.so does not export these.
- * __graft_entry__.build() links a second library, libmaple_hip_debug.so, from the same sources with -DMAPLE_DEBUG_ABI: every
- * entry point of maple_hip.h plus the ones below.  The tests of the two innermost device functions (getPartialVec M:4073-4141,
+ * __graft_entry__.build() links a second library, libmaple_hip_debug.so, from the product library's objects plus the one unit
+ * that defines these (maple_amd/csrc/debug_abi.hip): every entry point of maple_hip.h plus the ones below.  The tests of the two innermost device functions (getPartialVec M:4073-4141,
  * simplify M:3697-3717: SURVEY 8a rows a3 / a4, which no batched operator exposes on their own), of the wavefront-wide
  * appendProbNode, the PMC calibration (tools/calib_fetch.py) and the level profile (tools/level_profile.py) load that one
  * (maple_amd.runtime.Device(..., debug=True)). */

@@ -1,7 +1,8 @@
 // maple_amd/csrc/batch_host.h -- the small host-side helpers every translation unit with batch entry points shares (each gets its
 // own copy: they only touch the context): launch geometry, the dispatch over the three model switches, list-id checks, the
-// staging arena for a call's arguments, event pairs; and the declarations of the few larger ones that live in maple_hip.hip
-// (hidden visibility: not part of the C ABI).  Included by maple_hip.hip and spr_batch.hip.
+// staging arena for a call's arguments, event pairs; the launch attributes the scoring kernels share; and the declarations of the
+// host functions that cross translation units (hidden visibility: not part of the C ABI).  Included by every unit with batch
+// entry points: maple_hip.hip, append_queries.hip, placement.hip, update.hip, spr_batch.hip, debug_abi.hip.
 #pragma once
 #include "ctx_host.h"
 
@@ -15,6 +16,12 @@ struct alignas(16) TileBest { double score; int32_t rank, idx; };
 #ifndef MAPLE_BLOCK
 #define MAPLE_BLOCK 256
 #endif
+// the appendProbNode kernels (k_append*, k_place_score, k_pe_level, k_ahead_cols): 120 VGPRs / no scratch at 4 waves per SIMD
+// measured fastest (5 waves spills, 3 waves loses latency hiding)
+#ifndef MAPLE_APPEND_WAVES
+#define MAPLE_APPEND_WAVES 4
+#endif
+#define MAPLE_APPEND_ATTR __launch_bounds__(MAPLE_BLOCK) __attribute__((amdgpu_waves_per_eu(MAPLE_APPEND_WAVES, MAPLE_APPEND_WAVES)))
 #ifndef MAPLE_ZERO_DIST_BUDGET
 #define MAPLE_ZERO_DIST_BUDGET 16      // traversal placements a search from a zero-length branch gets before the dense tier
 #endif
@@ -115,17 +122,36 @@ static int need_model(maple_ctx *c)
 __attribute__((visibility("hidden")))
 int commit_lists(maple_ctx *c, int32_t n, const int64_t *d_woff, const int64_t *d_aoff, int32_t *d_n_ent, int32_t *d_n_aux,
                  int32_t *outList, const uint2 *srcW = nullptr, const double *srcA = nullptr);
+// ... with the sizes already on the host
+__attribute__((visibility("hidden")))
+int commit_known(maple_ctx *c, int32_t n, const int64_t *d_woff, const int64_t *d_aoff, const int32_t *d_n_ent, const int32_t *d_n_aux,
+                 const std::vector<int32_t> &ne, const std::vector<int32_t> &na, int32_t *outList, const uint2 *srcW, const double *srcA);
+// lists committed on the library's stream are not yet visible to work on another stream: wait once
+__attribute__((visibility("hidden")))
+int settle(maple_ctx *c);
+// evaluatePlacement for n items (maple_evaluate_placement_batch; comp2 optional, 2 doubles per item: see k_evalplace)
+__attribute__((visibility("hidden")))
+int evaluate_placement_items(maple_ctx *c, int32_t n, const int32_t *midTot, const int32_t *down, const int32_t *up, const double *dist,
+                             const int32_t *rem, const uint8_t *remTip, const uint8_t *fromTip1, double *out4, double *comp2);
+// k_wave_append (one wavefront per pair) on the context's stream, `grid` workgroups
+__attribute__((visibility("hidden")))
+void launch_wave_append(maple_ctx *c, int grid, int n, const int32_t *pl, const int32_t *cl, const uint8_t *tip, const double *bl, double *out);
+// ---- defined in append_queries.hip -----------------------------------------------------------------------------------------
 // one launch of the queries x candidates scoring kernel on stream s (k_append_queries / k_append_queries_lds)
 __attribute__((visibility("hidden")))
 int launch_append_queries(maple_ctx *c, hipStream_t s, int nQ, const int32_t *qList, int nC, const int32_t *cand, int isTip, double bLen,
                           double *out, long long ldOut, const int32_t *outCol, const uint8_t *qTip, const double *qBLen, int kind,
                           double algBytes, TileBest *tileBest = nullptr, const int32_t *visitRank = nullptr, const int4 *chunkTab = nullptr,
                           int nChunkTab = 0, int nF = 1, unsigned long long *finMask = nullptr, bool lanesOnly = false);
-// one launch of the placement phase's scoring kernel (k_place_score, placement_host.h) on the context's stream
+// ---- defined in placement.hip ----------------------------------------------------------------------------------------------
+// one launch of the placement phase's scoring kernel (k_place_score) on the context's stream
 __attribute__((visibility("hidden")))
 int launch_place_score(maple_ctx *c, int nQ, int nF, const int32_t *qFrameLists, int nC, const int32_t *cand, const int32_t *candFrame,
                        int isTip, double bLen, double *out, long long ldOut, const int32_t *outCol, const uint8_t *qTip, const double *qBLen,
                        int kind = MAPLE_K_PLACE_SCORE, double algBytes = 0.0);
+// ---- defined in update.hip -------------------------------------------------------------------------------------------------
+__attribute__((visibility("hidden")))
+void update_scratch_free(maple_ctx *c);
 // ---- defined in spr_batch.hip ----------------------------------------------------------------------------------------------
 // the device tree once more from the host copy of its columns (after maple_tree_patch left tables stale)
 __attribute__((visibility("hidden")))

@@ -1,11 +1,7 @@
 // maple_amd/csrc/ctx_host.h -- the library's context (host side) and the few helpers every translation unit of
-// libmaple_hip.so shares.  Included by maple_hip.hip (C ABI, batch operators, dense / replay tiers of the SPR search) and
-// frontier.hip (the frontier tier of the SPR search).
+// libmaple_hip.so shares.  Included, directly or through batch_host.h / frontier.h / witness.h, by every .hip unit.
 #pragma once
 #include "../../include/maple_hip.h"
-#ifdef MAPLE_DEBUG_ABI
-#include "../../include/maple_hip_debug.h"
-#endif
 #include "genome_dev.h"
 #include "search_dev.h"
 #include "placement_dev.h"
@@ -92,7 +88,7 @@ struct PlaceMeta {                     // derived from the uploaded tree, rebuil
 };
 
 // maple_placement_ahead: the score rows of the NEXT samples of a serial placement loop (M:11692-11752), made in one launch of
-// the batch kernel and kept current under maple_tree_patch -- see placement_host.h
+// the batch kernel and kept current under maple_tree_patch -- see placement.hip
 struct PlaceAhead {
     bool active = false;
     int32_t K = 0, next = 0;           // rows; the row the next single-query search takes
@@ -116,13 +112,13 @@ struct PlaceAhead {
     std::vector<int32_t> dirtyCols, dirtyLeaves;     // columns whose list changed (or that are new) since the rows were made: every search scores them for its sample
     bool rootDirty = false;            // ... the root vector (its score sits at [ld - 1])
     long long refreshes = 0, refreshedPairs = 0;
-    // the rows hold the scores of the branches an expansion under permissive rules reached (placement_host.h); every other column
+    // the rows hold the scores of the branches an expansion under permissive rules reached (placement.hip); every other column
     // holds PLACE_NO_SCORE, and a traversal that asks for one has the whole row scored first (counted)
     bool sparse = false;
     long long fallbacks = 0, expanded = 0, searches = 0;
     // The traversal of the NEXT announced sample, run by a host thread while the library's caller is busy with the sample just
     // searched (refinement, tree edit, updatePartials): speculative -- made on the tree as it is BEFORE that sample's placement --
-    // and used only if the placement's patch touches no node the traversal visited (placement_host.h).
+    // and used only if the placement's patch touches no node the traversal visited (placement.hip).
     struct Spec {
         std::thread th;
         int32_t row = -1, id = 0, status = -1, buf = 0;     // the row it is for (-1: none), its epoch in visitEpoch, 0 = outputs usable
@@ -274,7 +270,7 @@ struct maple_ctx {
     DevBuf<uint32_t> p_from;
     int32_t *d_tile_counters = nullptr;    // ring of tile counters for the dynamically scheduled kernels
     int tile_counter_next = 0;
-    void *upd = nullptr;               // UpdateScratch of maple_update_partials (update_host.h)
+    void *upd = nullptr;               // UpdateScratch of maple_update_partials (update.hip)
     std::vector<SearchOut> h_search_out;   // per-search results of the last maple_spr_search_batch on the host (kept: 24 MB of fresh
                                        // pages per call cost 5 ms at 200 000 searches)
     void *frontier = nullptr;          // FrontierScratch of the frontier tier of the SPR search (frontier.hip)

@@ -1,4 +1,5 @@
-// maple_amd/csrc/frontier.h -- interface of the frontier tier of the SPR search (frontier.hip) towards maple_hip.hip.
+// maple_amd/csrc/frontier.h -- interface of the frontier tier of the SPR search (frontier.hip) towards the other units
+// (spr_batch.hip, maple_hip.hip, debug_abi.hip).
 #pragma once
 #include "ctx_host.h"
 

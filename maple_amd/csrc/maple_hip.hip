@@ -1,12 +1,13 @@
-// maple_amd/csrc/maple_hip.hip -- libmaple_hip.so: context, model, arena, the batched list operators and their kernels, the
-// placement search, updatePartials, the RCCL arg-max, measurement aids (C ABI: include/maple_hip.h).  The tree mirror and the SPR
-// search batch live in spr_batch.hip, the frontier tier in frontier*.hip, the witness filter in witness.hip.
+// maple_amd/csrc/maple_hip.hip -- libmaple_hip.so: context, model, arena, the batched list operators over explicit pairs and their
+// kernels, the RCCL arg-max, the timing readers (C ABI: include/maple_hip.h).  The dense query kernels live in append_queries.hip,
+// the placement search in placement.hip, updatePartials and the list rebuild in update.hip, the tree mirror and the SPR search
+// batch in spr_batch.hip, the frontier tier in frontier*.hip, the witness filter in witness.hip; the hooks of
+// include/maple_hip_debug.h in debug_abi.hip.  What crosses units is declared in batch_host.h.
 // gfx950 only.  One lane walks one (parent list, child list) pair; see genome_dev.h.
 #include "../../include/maple_hip.h"
 #include "genome_dev.h"
 #include "search_dev.h"
 #include "placement_dev.h"
-#include "append_lds.h"
 #include "wave_dev.h"
 #include "wave_update.h"
 
@@ -46,12 +47,6 @@ static RcclApi g_rccl{};
 // =================================================================================================
 
 // appendProbNode over arbitrary pairs ----------------------------------------------------------
-// 120 VGPRs / no scratch at 4 waves per SIMD measured fastest (5 waves spills, 3 waves loses latency hiding).
-#ifndef MAPLE_APPEND_WAVES
-#define MAPLE_APPEND_WAVES 4
-#endif
-#define MAPLE_APPEND_ATTR __launch_bounds__(MAPLE_BLOCK) __attribute__((amdgpu_waves_per_eu(MAPLE_APPEND_WAVES, MAPLE_APPEND_WAVES)))
-#define MAPLE_QLDS 192                 // query-list words staged in LDS per wavefront (longer lists are read from HBM/L2)
 template <bool RV, bool U, bool SS>
 __global__ MAPLE_APPEND_ATTR void k_append(const DevModel *__restrict__ mp, ArenaView av, int n, const int32_t *pl,
                                            const int32_t *cl, const uint8_t *tip, const double *bl, double *out)
@@ -62,320 +57,6 @@ __global__ MAPLE_APPEND_ATTR void k_append(const DevModel *__restrict__ mp, Aren
     Ctx<RV, U, SS> c(m, lds);
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
         out[i] = append_walk(c, list_ref(av, pl[i]), list_ref(av, cl[i]), tip[i] != 0, bl[i]);
-}
-
-// Q queries x C candidates, query-major output out[q*C + k]: pair (q, k) is handled by one lane.  A tile is one query x
-// 64 consecutive candidates and every WAVEFRONT pulls its next tile from an atomic counter, so there is no barrier
-// anywhere and a wavefront that drew short lists never idles behind its workgroup's longest lane.  Tiles are numbered
-// candidate-chunk-major: the ~4 000 wavefronts in flight sweep the same few candidate chunks (hot in L1/L2) with
-// different queries.  Callers pass the candidates SORTED BY LIST LENGTH so that the 64 lanes of a wavefront finish
-// together.  Measured on the 10 000-sample bench tree (256 queries x 14 878 branches), ms per launch:
-//   static 256-candidate tiles, query-major 2.56 | chunk-major 2.29 | dynamic 64-candidate tiles, query-major 2.30 |
-//   dynamic + chunk-major 1.85 | + candidates sorted by length 1.53.
-// (Staging the query in LDS behind __syncthreads() was 1.4x slower; several queries per tile lost balance: 2.06 at 4.)
-
-template <bool RV, bool U, bool SS>
-__global__ MAPLE_APPEND_ATTR void k_append_queries(const DevModel *__restrict__ mp, ArenaView av, int nQ,
-                                                   const int32_t *qList, int nC, const int32_t *cand, int isTip,
-                                                   double bLen, double *out, long long ldOut, const int32_t *outCol,
-                                                   const uint8_t *qTip, const double *qBLen, int *counter,
-                                                   TileBest *tileBest, const int32_t *visitRank, unsigned long long *finMask)
-{
-    __shared__ Lds lds;
-    __shared__ unsigned long long qlds[MAPLE_BLOCK / 64][MAPLE_QLDS];   // the tile's query list, one copy per wavefront
-    const DevModel &m = *mp;
-    stage_model(m, lds);
-    Ctx<RV, U, SS> c(m, lds);
-    const int lane = threadIdx.x & 63;
-    unsigned long long *myq = qlds[threadIdx.x >> 6];
-    const int nChunks = (nC + 63) / 64;
-    const long long tiles = (long long)nQ * nChunks;
-    double tbScore = -INFINITY;
-    int tbRank = 0x7fffffff, tbIdx = -1;
-    for (;;) {
-        int j = 0;
-        if (lane == 0) j = atomicAdd(counter, 1);
-        j = __builtin_amdgcn_readfirstlane(j);
-        if (j >= tiles) break;
-        const int ch = j / nQ;
-        const int q = j - ch * nQ;
-        const int k = ch * 64 + lane;
-        const int ql = qList[q];
-        const int nq = av.n_ent[ql];
-        const ListRef qref = list_ref(av, ql);
-        const bool staged = nq <= MAPLE_QLDS;                             // wave-uniform
-        if (staged) {
-            // all 64 lanes walk the same query: its words go to LDS once per tile (no workgroup barrier: the LDS
-            // pipeline serves one wavefront's requests in order) and every step's query load is a ds_read
-            for (int i = lane; i < nq; i += 64) myq[i] = ((const unsigned long long *)qref.w)[i];
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        }
-        const int cl = k < nC ? cand[k] : -1;                             // -1: this column has no list (score unused)
-        bool finite = false;
-        if (cl >= 0) {
-            const bool tipq = qTip ? qTip[q] != 0 : isTip != 0;
-            const double blq = qBLen ? qBLen[q] : bLen;
-            double lk;
-            if (staged) {
-                PairWalk<RV, U, SS> w(c, qref, tipq, blq, myq);
-                w.start(list_ref(av, cl));
-                while (!w.step()) {}
-                lk = w.finish();
-            } else lk = append_walk(c, list_ref(av, cl), qref, tipq, blq);
-            if (!tileBest) { if (!finMask || lk > -INFINITY) out[(long long)q * ldOut + (outCol ? outCol[k] : k)] = lk; }   // (see the LDS kernel)
-            else { tbScore = lk; tbRank = visitRank ? visitRank[k] : k; tbIdx = k; }
-            finite = lk > -INFINITY;
-        }
-        if (finMask) {
-            const unsigned long long fm = __ballot(finite);
-            if (lane == 0) finMask[(long long)q * nChunks + ch] = fm;
-        }
-        if (tileBest) {
-            // the wavefront reduction of north_star: best score of the tile's 64 candidates, exact ties to the EARLIEST visit
-            // (the reference keeps the first of equal scores: strict >, M:7083 / 8065); one 16-byte record per (query, tile)
-            // instead of 64 scores
-            for (int m2 = 32; m2 >= 1; m2 >>= 1) {
-                const double os = __shfl_xor(tbScore, m2, 64);
-                const int orank = __shfl_xor(tbRank, m2, 64), oidx = __shfl_xor(tbIdx, m2, 64);
-                if (os > tbScore || (os == tbScore && orank < tbRank)) { tbScore = os; tbRank = orank; tbIdx = oidx; }
-            }
-            if (lane == 0) tileBest[(long long)q * nChunks + ch] = TileBest{tbScore, tbRank, tbIdx};
-            tbScore = -INFINITY; tbRank = 0x7fffffff; tbIdx = -1;
-        }
-        __builtin_amdgcn_wave_barrier();
-    }
-}
-
-
-// The same Q x C scoring with the tile's 64 candidate lists staged in LDS (append_lds.h): a workgroup of 16 wavefronts (one
-// per CU) takes a unit = (chunk of 64 candidates, block of MAPLE_LDS_QB queries), copies the chunk's words and aux doubles into
-// LDS with coalesced loads -- and, with per-site rates, the rate of every entry's last site next to it -- and its
-// wavefronts then pull the block's queries from an LDS counter: one query x the 64 staged candidates per tile, candidate
-// words / stored lengths / O vectors / site rates and the query's words and rates all read with ds_read.  Chunks too long for
-// the LDS budget, and queries longer than the strip, are walked from global memory as before.
-#define MAPLE_LDS_BLOCK 1024
-#define MAPLE_LDS_CAPW 4096            // candidate words per staged chunk (32 KB, + 32 KB of site rates with rate variation)
-#define MAPLE_LDS_CAPA 1536            // candidate aux doubles per staged chunk (12 KB)
-#ifndef MAPLE_LDS_QB
-#define MAPLE_LDS_QB 512               // queries per unit: 128 / 256 / 512 measured 549 / 544 / 538 ms per launch at 100k tips
-#endif
-template <bool RV, bool U, bool SS>
-__global__ __launch_bounds__(MAPLE_LDS_BLOCK) __attribute__((amdgpu_waves_per_eu(4, 4)))
-void k_append_queries_lds(const DevModel *__restrict__ mp, ArenaView av, int nQ, const int32_t *qList, int nC, const int32_t *cand,
-                          int isTip, double bLen, double *out, long long ldOut, const int32_t *outCol, const uint8_t *qTip,
-                          const double *qBLen, int *counter, TileBest *tileBest, const int32_t *visitRank,
-                          const int4 *chunkTab, int nChunkTab, int nF, unsigned long long *finMask)
-{
-    // chunkTab (trees with MAT local references): the chunks are given as {first candidate, candidates (<= 64), reference
-    // frame, -}, each within ONE frame, and query q's list is qList[q * nF + frame] -- the query expressed in that frame
-    constexpr int NW = MAPLE_LDS_BLOCK / 64;
-    __shared__ Lds lds;
-    __shared__ int cwoff[65], caoff[65];
-    __shared__ int sUnit, sNext, sStaged;
-    extern __shared__ unsigned long long dynU64[];
-    // dynamic LDS: candidate words | candidate aux | [candidate rates] | per-wavefront query words | [per-wavefront query rates]
-    unsigned long long *cW = dynU64;
-    double *cA = (double *)(cW + MAPLE_LDS_CAPW);
-    double *cR = cA + MAPLE_LDS_CAPA;
-    unsigned long long *qW = (unsigned long long *)(cR + (RV ? MAPLE_LDS_CAPW : 0));
-    double *qR = (double *)(qW + NW * MAPLE_QLDS);
-    const DevModel &m = *mp;
-    stage_model(m, lds);
-    Ctx<RV, U, SS> c(m, lds);
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int nChunks = chunkTab ? nChunkTab : (nC + 63) / 64, nQB = (nQ + MAPLE_LDS_QB - 1) / MAPLE_LDS_QB;
-    const long long units = (long long)nChunks * nQB;
-    unsigned long long *myq = qW + wave * MAPLE_QLDS;
-    double *myqR = qR + wave * MAPLE_QLDS;
-    double tbScore = -INFINITY;
-    int tbRank = 0x7fffffff, tbIdx = -1;
-    for (;;) {
-        if (tid == 0) sUnit = atomicAdd(counter, 1);
-        __syncthreads();
-        const int unit = sUnit;
-        if (unit >= units) break;
-        const int ch = unit / nQB, qb = unit - ch * nQB;
-        int c0 = ch * 64, nCk = min(64, nC - ch * 64), frame = 0;
-        if (chunkTab) { const int4 u = chunkTab[ch]; c0 = u.x; nCk = u.y; frame = u.z; }
-        // this lane's candidate and where its list sits in the staged chunk
-        const int k = c0 + lane;
-        const int cl = lane < nCk ? cand[k] : -1;
-        if (wave == 0) {
-            int ne = cl >= 0 ? av.n_ent[cl] : 0, na = cl >= 0 ? av.n_aux[cl] : 0;
-            int pw = ne, pa = na;                                          // inclusive prefix sums over the 64 lists
-            for (int d = 1; d < 64; d <<= 1) {
-                const int ow = __shfl_up(pw, d, 64), oa = __shfl_up(pa, d, 64);
-                if (lane >= d) { pw += ow; pa += oa; }
-            }
-            cwoff[lane] = pw - ne; caoff[lane] = pa - na;
-            if (lane == 63) { cwoff[64] = pw; caoff[64] = pa; sStaged = (pw <= MAPLE_LDS_CAPW && pa <= MAPLE_LDS_CAPA) ? 1 : 0; sNext = 0; }
-        }
-        __syncthreads();
-        const bool stagedC = sStaged != 0;
-        if (stagedC) {                                                     // 4 lists per wavefront, coalesced within a list
-            constexpr int perWave = (64 + NW - 1) / NW;
-            for (int i = wave * perWave; i < min(64, wave * perWave + perWave); i++) {
-                if (i >= nCk) break;
-                const int li = cand[c0 + i];
-                const unsigned long long *sw = (const unsigned long long *)(av.words + av.ent_off[li]);
-                const double *sa = av.aux + av.aux_off[li];
-                const int w0 = cwoff[i], nw = cwoff[i + 1] - w0, a0 = caoff[i], na2 = caoff[i + 1] - a0;
-#ifndef MAPLE_DENSE_PLAIN
-                // (staged in the SKIPPING form of append_lds.h: the tail-less reference runs in front of single-site entries are left
-                // out -- half the entries, and with them half the steps of every walk over the chunk)
-                int kept = 0;
-                for (int j0 = 0; j0 < nw; j0 += 64) {
-                    const int j = j0 + lane;
-                    unsigned long long w = 0;
-                    bool keep = false;
-                    if (j < nw) { w = sw[j]; keep = !skip_form_drops(w, j + 1 < nw ? sw[j + 1] : 0ull, j + 1 == nw); }
-                    const unsigned long long bal = __ballot(keep);
-                    if (keep) {
-                        const int d = w0 + kept + __popcll(bal & ((1ull << lane) - 1ull));
-                        cW[d] = w;
-                        if (RV) cR[d] = c.rate((int)(uint32_t)w - 1);
-                    }
-                    kept += __popcll(bal);
-                }
-#else
-                for (int j = lane; j < nw; j += 64) {
-                    const unsigned long long w = sw[j];
-                    cW[w0 + j] = w;
-                    if (RV) cR[w0 + j] = c.rate((int)(uint32_t)w - 1);
-                }
-#endif
-                for (int j = lane; j < na2; j += 64) cA[a0 + j] = sa[j];
-            }
-        }
-        __syncthreads();
-        const int myW = cwoff[lane], myA = caoff[lane];
-        for (;;) {
-            int qi = 0;
-            if (lane == 0) qi = atomicAdd(&sNext, 1);
-            qi = __builtin_amdgcn_readfirstlane(qi);
-            const int q = qb * MAPLE_LDS_QB + qi;
-            if (qi >= MAPLE_LDS_QB || q >= nQ) break;
-            const int ql = chunkTab ? qList[(long long)q * nF + frame] : qList[q];
-            const int nq = av.n_ent[ql];
-            const ListRef qref = list_ref(av, ql);
-            const bool stagedQ = nq <= MAPLE_QLDS;                          // wave-uniform
-            if (stagedQ) {
-#ifndef MAPLE_DENSE_PLAIN
-                const unsigned long long *qsrc = (const unsigned long long *)qref.w;
-                int kept = 0;
-                for (int j0 = 0; j0 < nq; j0 += 64) {
-                    const int j = j0 + lane;
-                    unsigned long long w = 0;
-                    bool keep = false;
-                    if (j < nq) { w = qsrc[j]; keep = !skip_form_drops(w, j + 1 < nq ? qsrc[j + 1] : 0ull, j + 1 == nq); }
-                    const unsigned long long bal = __ballot(keep);
-                    if (keep) {
-                        const int d = kept + __popcll(bal & ((1ull << lane) - 1ull));
-                        myq[d] = w;
-                        if (RV) myqR[d] = c.rate((int)(uint32_t)w - 1);
-                    }
-                    kept += __popcll(bal);
-                }
-#else
-                for (int i = lane; i < nq; i += 64) {
-                    const unsigned long long w = ((const unsigned long long *)qref.w)[i];
-                    myq[i] = w;
-                    if (RV) myqR[i] = c.rate((int)(uint32_t)w - 1);
-                }
-#endif
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            }
-            bool finite = false;
-#ifndef MAPLE_DENSE_PLAIN
-            // (the walk in skipping form votes over the whole wavefront, append_lds.h: every lane calls, those without a candidate
-            // with valid = false)
-            const bool validL = cl >= 0;
-            double lkAll;
-            {
-                const bool tipq = qTip ? qTip[q] != 0 : isTip != 0;
-                const double blq = qBLen ? qBLen[q] : bLen;
-                const MemLG qL{(lds_u64p)myq, qref.aux, (lds_f64p)myqR};
-                const MemG qG{(const unsigned long long *)qref.w, qref.aux};
-                if (stagedC) {                                              // (block-uniform; stagedQ is wave-uniform)
-                    const MemL pL{(lds_u64p)(cW + myW), (lds_f64p)(cA + myA), (lds_f64p)(cR + myW)};
-                    lkAll = stagedQ ? append_walk_c(c, pL, qL, tipq, blq, validL) : append_walk_c(c, pL, qG, tipq, blq, validL);
-                } else {
-                    const ListRef pr = validL ? list_ref(av, cl) : qref;
-                    const MemG pG{(const unsigned long long *)pr.w, pr.aux};
-                    lkAll = stagedQ ? append_walk_c(c, pG, qL, tipq, blq, validL) : append_walk_c(c, pG, qG, tipq, blq, validL);
-                }
-            }
-#endif
-            if (cl >= 0) {
-#ifndef MAPLE_DENSE_PLAIN
-                const double lk = lkAll;
-#else
-                const bool tipq = qTip ? qTip[q] != 0 : isTip != 0;
-                const double blq = qBLen ? qBLen[q] : bLen;
-                const MemLG qL{(lds_u64p)myq, qref.aux, (lds_f64p)myqR};
-                const MemG qG{(const unsigned long long *)qref.w, qref.aux};
-                double lk;
-                if (stagedC) {
-                    const MemL pL{(lds_u64p)(cW + myW), (lds_f64p)(cA + myA), (lds_f64p)(cR + myW)};
-                    lk = stagedQ ? append_walk_m(c, pL, qL, tipq, blq) : append_walk_m(c, pL, qG, tipq, blq);
-                } else {
-                    const ListRef pr = list_ref(av, cl);
-                    const MemG pG{(const unsigned long long *)pr.w, pr.aux};
-                    lk = stagedQ ? append_walk_m(c, pG, qL, tipq, blq) : append_walk_m(c, pG, qG, tipq, blq);
-                }
-#endif
-                // finMask: which of the tile's 64 scores are finite goes out as ONE word per (query, tile) and only the finite
-                // scores are stored -- the searches these rows are for are the ones whose scores are nearly all -inf (a mismatch
-                // over a zero-length branch), and an 8-byte store into every line of a row was most of the kernel's HBM traffic
-                if (!tileBest) { if (!finMask || lk > -INFINITY) out[(long long)q * ldOut + (outCol ? outCol[k] : k)] = lk; }
-                else { tbScore = lk; tbRank = visitRank ? visitRank[k] : k; tbIdx = k; }
-                finite = lk > -INFINITY;
-            }
-            if (finMask) {
-                const unsigned long long fm = __ballot(finite);
-                if (lane == 0) finMask[(long long)q * nChunks + ch] = fm;
-            }
-            if (tileBest) {
-                for (int m2 = 32; m2 >= 1; m2 >>= 1) {
-                    const double os = __shfl_xor(tbScore, m2, 64);
-                    const int orank = __shfl_xor(tbRank, m2, 64), oidx = __shfl_xor(tbIdx, m2, 64);
-                    if (os > tbScore || (os == tbScore && orank < tbRank)) { tbScore = os; tbRank = orank; tbIdx = oidx; }
-                }
-                if (lane == 0) tileBest[(long long)q * nChunks + ch] = TileBest{tbScore, tbRank, tbIdx};
-                tbScore = -INFINITY; tbRank = 0x7fffffff; tbIdx = -1;
-            }
-            __builtin_amdgcn_wave_barrier();
-        }
-        __syncthreads();                                                   // nobody may still read the chunk when it is restaged
-    }
-}
-template <bool RV> static size_t lds_kernel_dyn_bytes()
-{
-    constexpr int NW = MAPLE_LDS_BLOCK / 64;
-    return (size_t)MAPLE_LDS_CAPW * 8 + (size_t)MAPLE_LDS_CAPA * 8 + (RV ? (size_t)MAPLE_LDS_CAPW * 8 : 0)
-           + (size_t)NW * MAPLE_QLDS * 8 * (RV ? 2 : 1);
-}
-
-// per query: the best of its tiles (same order: score, then earliest visit)
-__global__ __launch_bounds__(64) void k_argmax_reduce(int nQ, int nChunks, const TileBest *tb, double *bestScore, int32_t *bestIdx)
-{
-    const int q = blockIdx.x;
-    if (q >= nQ) return;
-    TileBest b{-INFINITY, 0x7fffffff, -1};
-    for (int i = threadIdx.x; i < nChunks; i += 64) {
-        const TileBest t = tb[(long long)q * nChunks + i];
-        if (t.score > b.score || (t.score == b.score && t.rank < b.rank)) b = t;
-    }
-    for (int m2 = 32; m2 >= 1; m2 >>= 1) {
-        const double os = __shfl_xor(b.score, m2, 64);
-        const int orank = __shfl_xor(b.rank, m2, 64), oidx = __shfl_xor(b.idx, m2, 64);
-        if (os > b.score || (os == b.score && orank < b.rank)) { b.score = os; b.rank = orank; b.idx = oidx; }
-    }
-    if (threadIdx.x == 0) { bestScore[q] = b.score; bestIdx[q] = b.idx; }
 }
 
 // per-item scratch placement for list-producing kernels
@@ -508,91 +189,6 @@ __global__ __launch_bounds__(MAPLE_BLOCK) void k_shorten(const DevModel *__restr
     }
 }
 
-// One item of a level of updatePartials (update_host.h): mergeVectors, then what the reference does with the result, in
-// one go -- no trip to the host between the three.  mode 0 (a lower list, M:5760-5800): shorten(), then
-// areVectorsDifferent(new, old); mode 1 (probVectTotUp, M:5525-5557): shorten(); mode 2 (probVectUpRight / UpLeft,
-// M:5559-5660): areVectorsDifferent(old, new), and shorten() only if they differ.  The merged list goes to scratch slot A,
-// the shortened one to slot B (what is committed).  n_ent: entries of B, -1 = None, < -1 = fatal; flag: "different".
-#define MAPLE_UPDATE_ITEM_ARGS                                                                                                  \
-    const DevModel *__restrict__ mp, ArenaView av, int n, const int32_t *l1, const double *b1, const uint8_t *t1,               \
-        const int32_t *l2, const double *b2, const uint8_t *t2, const uint8_t *ud, const uint8_t *mode, const int32_t *old,     \
-        uint2 *words, double *aux, const int64_t *woff, const int64_t *cap, int32_t *res3
-
-template <bool RV, bool U, bool SS>
-__device__ inline void update_item_lane(const Ctx<RV, U, SS> &c, const ArenaView &av, int n, int i, const int32_t *l1, const double *b1,
-                                        const uint8_t *t1, const int32_t *l2, const double *b2, const uint8_t *t2, const uint8_t *ud,
-                                        const uint8_t *mode, const int32_t *old, uint2 *words, double *aux, const int64_t *woff,
-                                        const int64_t *cap, int32_t *res3)
-{
-    Writer wa, wb;
-    wa.init(words + woff[i], aux + 5 * woff[i]);
-    wb.init(words + woff[i] + cap[i], aux + 5 * (woff[i] + cap[i]));
-    double lk = 0.0;
-    const int r = merge_walk(c, list_ref(av, l1[i]), b1[i], t1[i] != 0, list_ref(av, l2[i]), b2[i], t2[i] != 0, ud[i] != 0, false, 0,
-                             0, wa, &lk);
-    int ne = r, na = 0, flag = 1;
-    if (r >= 0) {
-        const ListRef A{wa.w, wa.aux};
-        if (mode[i] == 2 && old[i] >= 0) flag = differ_walk(c, list_ref(av, old[i]), A) ? 1 : 0;
-        if (flag) {
-            ne = shorten_walk(c, A, r, wb);
-            na = wb.na;
-            if (mode[i] == 0 && old[i] >= 0) flag = differ_walk(c, ListRef{wb.w, wb.aux}, list_ref(av, old[i])) ? 1 : 0;
-        } else ne = 0;
-    }
-    res3[i] = ne; res3[n + i] = na; res3[2 * n + i] = flag;
-}
-
-template <bool RV, bool U, bool SS>
-__global__ __launch_bounds__(MAPLE_BLOCK) void k_update_items(MAPLE_UPDATE_ITEM_ARGS)
-{
-    __shared__ Lds lds;
-    const DevModel &m = *mp;
-    stage_model(m, lds);
-    Ctx<RV, U, SS> c(m, lds);
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
-        update_item_lane(c, av, n, i, l1, b1, t1, l2, b2, t2, ud, mode, old, words, aux, woff, cap, res3);
-}
-
-// The same item by a whole wavefront (wave_update.h): what a level with a handful of items -- a single change walking up
-// and down the tree -- waits for is one item's latency, not throughput.  One wavefront per workgroup, one item at a time;
-// lists too long for the staged walk go through the one-lane code on lane 0.
-template <bool RV, bool U, bool SS>
-__global__ __launch_bounds__(64) void k_update_items_wave(MAPLE_UPDATE_ITEM_ARGS)
-{
-    __shared__ Lds lds;
-    __shared__ WaveUpdLds L;
-    const DevModel &m = *mp;
-    stage_model(m, lds);
-    Ctx<RV, U, SS> c(m, lds);
-    const int lane = threadIdx.x;
-    for (int i = blockIdx.x; i < n; i += gridDim.x) {
-        const int id1 = l1[i], id2 = l2[i], idOld = old[i];
-        const int n1 = av.n_ent[id1], n2 = av.n_ent[id2], nOld = idOld >= 0 ? av.n_ent[idOld] : 0;
-        if (n1 > MAPLE_WU_IN || n2 > MAPLE_WU_IN || nOld > MAPLE_WU_CAP) {
-            if (lane == 0) update_item_lane(c, av, n, i, l1, b1, t1, l2, b2, t2, ud, mode, old, words, aux, woff, cap, res3);
-            continue;
-        }
-        wave_sync();                                                       // the item before is done with the LDS
-        const ListRef Lo = idOld >= 0 ? list_ref(av, idOld) : ListRef{nullptr, nullptr};
-        if (idOld >= 0) {
-            const unsigned long long *wo = (const unsigned long long *)Lo.w;
-            for (int k = lane; k < nOld; k += 64) L.old[k] = wo[k];
-        }
-        int naA = 0;
-        const int r = wave_merge(c, list_ref(av, id1), n1, b1[i], t1[i] != 0, list_ref(av, id2), n2, b2[i], t2[i] != 0, ud[i] != 0, L, naA);
-        int ne = r, na = 0, flag = 1;
-        if (r >= 0) {
-            const int md = mode[i];
-            if (md == 2 && idOld >= 0) flag = wave_differ(c, L.old, Lo.aux, nOld, L.m, L.maux, r) ? 1 : 0;
-            if (flag) {
-                ne = wave_shorten(c, L, r, words + woff[i] + cap[i], aux + 5 * (woff[i] + cap[i]), na);
-                if (md == 0 && idOld >= 0) flag = wave_differ(c, L.in, L.baux, ne, L.old, Lo.aux, nOld) ? 1 : 0;
-            } else ne = 0;
-        }
-        if (lane == 0) { res3[i] = ne; res3[n + i] = na; res3[2 * n + i] = flag; }
-    }
-}
 
 // The explicit-pair operators by one wavefront per pair, for the few pairs of a single reference call (mergeVectors without
 // the likelihood, estimateBranchLengthWithDerivative; appendProbNode: k_wave_append below): same results, a fifth of the wait.
@@ -689,9 +285,29 @@ __global__ __launch_bounds__(64) void k_differ_wave(const DevModel *__restrict__
     }
 }
 
+// appendProbNode by a whole wavefront per pair (wave_dev.h), small batches of maple_append_batch and the hook of the parity tests
+// (debug_abi.hip).  No launch bound: the __launch_bounds__(64) this definition used to carry never took effect (a declaration
+// without it came first and instantiated the kernel), so the kernel has always been compiled for the default 1024; giving it the
+// bound changes its code (the barriers go) and belongs in a change of its own.
 template <bool RV, bool U, bool SS>
 __global__ void k_wave_append(const DevModel *__restrict__ mp, ArenaView av, int n, const int32_t *pl, const int32_t *cl,
-                              const uint8_t *tip, const double *bl, double *out);
+                              const uint8_t *tip, const double *bl, double *out)
+{
+    __shared__ Lds lds;
+    __shared__ WaveLds wl;
+    const DevModel &m = *mp;
+    stage_model(m, lds);
+    Ctx<RV, U, SS> c(m, lds);
+    for (int i = blockIdx.x; i < n; i += gridDim.x) {
+        const double v = wave_append(c, list_ref(av, pl[i]), av.n_ent[pl[i]], list_ref(av, cl[i]), av.n_ent[cl[i]], tip[i] != 0, bl[i], wl);
+        if (threadIdx.x == 0) out[i] = v;
+        __builtin_amdgcn_wave_barrier();
+    }
+}
+void launch_wave_append(maple_ctx *c, int grid, int n, const int32_t *pl, const int32_t *cl, const uint8_t *tip, const double *bl, double *out)
+{
+    DISPATCH3(c, k_wave_append, <<<grid, 64, 0, c->stream>>>(c->d_model, view(c), n, pl, cl, tip, bl, out));
+}
 #define MAPLE_WAVE_PAIRS_MAX 1024        // explicit-pair batches up to this size go one wavefront per pair
 
 // shorten of ONE list per wavefront (wave_shorten, wave_update.h): for the handful of lists a single-query placement shortens
@@ -1004,8 +620,6 @@ extern "C" int maple_create(maple_ctx **out, int device, int32_t lRef, const uin
     return MAPLE_OK;
 }
 
-static void update_scratch_free(maple_ctx *c);   // update_host.h
-
 extern "C" int maple_set_tuning(maple_ctx *c, const maple_tuning *t)
 {
     if (!c || !t) return MAPLE_ERR_ARG;
@@ -1314,8 +928,6 @@ extern "C" int maple_arena_release(maple_ctx *c, int64_t markBoth)
     return MAPLE_OK;
 }
 
-static int settle(maple_ctx *c);
-static int grid_for(int n);
 // Keep only the lists `live` (ids in any order, no duplicates, -1 entries allowed and kept as -1): they are copied to the
 // bottom of the arena in the order given and renumbered 0, 1, 2, ...; newIds[i] = the new id of live[i].  Everything else
 // -- every other list id, every arena mark, resident candidate sets and the uploaded tree -- is gone: upload the tree again
@@ -1427,9 +1039,6 @@ extern "C" int maple_mutations_upload(maple_ctx *c, int32_t n, const int64_t *of
 // Move freshly produced scratch lists into the arena and hand out ids (or -1 for None).  d_woff / d_aoff: the per-item
 // scratch offsets, already on the device.  One synchronisation (the sizes come back), then one staged copy (destinations and
 // list ids) and the copy kernel, which also writes the new rows of the device-side list table; nothing waits for it.
-static int commit_known(maple_ctx *c, int32_t n, const int64_t *d_woff, const int64_t *d_aoff, const int32_t *d_n_ent,
-                        const int32_t *d_n_aux, const std::vector<int32_t> &ne, const std::vector<int32_t> &na, int32_t *outList,
-                        const uint2 *srcW, const double *srcA);
 int commit_lists(maple_ctx *c, int32_t n, const int64_t *d_woff, const int64_t *d_aoff, int32_t *d_n_ent, int32_t *d_n_aux,
                  int32_t *outList, const uint2 *srcW, const double *srcA)
 {
@@ -1443,7 +1052,7 @@ int commit_lists(maple_ctx *c, int32_t n, const int64_t *d_woff, const int64_t *
 }
 
 // ... with the sizes already on the host (ne[i] == -1: nothing to commit for item i)
-static int commit_known(maple_ctx *c, int32_t n, const int64_t *d_woff, const int64_t *d_aoff, const int32_t *d_n_ent,
+int commit_known(maple_ctx *c, int32_t n, const int64_t *d_woff, const int64_t *d_aoff, const int32_t *d_n_ent,
                         const int32_t *d_n_aux, const std::vector<int32_t> &ne, const std::vector<int32_t> &na, int32_t *outList,
                         const uint2 *srcW, const double *srcA)
 {
@@ -1487,7 +1096,7 @@ static int commit_known(maple_ctx *c, int32_t n, const int64_t *d_woff, const in
 }
 
 // lists committed on the library's stream are not yet visible to work on another stream: wait once
-static int settle(maple_ctx *c)
+int settle(maple_ctx *c)
 {
     if (c->commit_pending) { HIPCK(c, hipStreamSynchronize(c->stream)); c->commit_pending = false; }
     return MAPLE_OK;
@@ -1592,7 +1201,7 @@ extern "C" int maple_append_batch(maple_ctx *c, int32_t n, const int32_t *pl, co
     TRY(stage_flush(c));
     HIPCK(c, c->s_f64[1].reserve(n));
     if (n <= wave_item_max(c, MAPLE_WAVE_PAIRS_MAX))
-        DISPATCH3(c, k_wave_append, <<<n, 64, 0, c->stream>>>(c->d_model, view(c), n, dpl, dcl, dtip, dbl, c->s_f64[1].p));
+        launch_wave_append(c, n, n, dpl, dcl, dtip, dbl, c->s_f64[1].p);
     else
         DISPATCH3(c, k_append, <<<grid_for(n), MAPLE_BLOCK, 0, c->stream>>>(c->d_model, view(c), n, dpl, dcl, dtip, dbl, c->s_f64[1].p));
     HIPCK(c, hipGetLastError());
@@ -1893,7 +1502,7 @@ extern "C" int maple_root_vector_batch(maple_ctx *c, int32_t n, const int32_t *l
 }
 
 // comp2 (optional, 2 doubles per item): see k_evalplace
-static int evaluate_placement_items(maple_ctx *c, int32_t n, const int32_t *midTot, const int32_t *down, const int32_t *up,
+int evaluate_placement_items(maple_ctx *c, int32_t n, const int32_t *midTot, const int32_t *down, const int32_t *up,
                                     const double *dist, const int32_t *rem, const uint8_t *remTip, const uint8_t *fromTip1,
                                     double *out4, double *comp2)
 {
@@ -1976,50 +1585,6 @@ int maple_internal_ev_pair(maple_ctx *c, hipEvent_t *a, hipEvent_t *b, int kind,
     c->ev_used += 2;
     return MAPLE_OK;
 }
-// one launch of k_append_queries on stream s (timed with an event pair): out[q * ldOut + (outCol ? outCol[k] : k)]
-int launch_append_queries(maple_ctx *c, hipStream_t s, int nQ, const int32_t *qList, int nC, const int32_t *cand,
-                          int isTip, double bLen, double *out, long long ldOut, const int32_t *outCol,
-                          const uint8_t *qTip, const double *qBLen, int kind, double algBytes, TileBest *tileBest,
-                          const int32_t *visitRank, const int4 *chunkTab, int nChunkTab, int nF,
-                          unsigned long long *finMask, bool lanesOnly)
-{
-    const long long tiles = (long long)nQ * (chunkTab ? nChunkTab : (nC + 63) / 64);
-    if (tiles > 0x7fffffffLL - (1 << 20)) return fail(c, MAPLE_ERR_ARG, "nQ x nC too large for one launch");
-    if (!c->d_tile_counters) HIPCK(c, hipMalloc((void **)&c->d_tile_counters, 64 * sizeof(int32_t)));
-    int32_t *counter = c->d_tile_counters + (c->tile_counter_next++ & 63);
-    HIPCK(c, hipMemsetAsync(counter, 0, sizeof(int32_t), s));
-    const long long waves = (tiles + 3) / 4;
-    const int grid = waves < 256 * MAPLE_APPEND_WAVES ? (int)waves : 256 * MAPLE_APPEND_WAVES;   // workgroups of 4 wavefronts, MAPLE_APPEND_WAVES per CU = the occupancy limit
-    hipEvent_t e0, e1;
-    TRY(ev_pair(c, &e0, &e1, kind, (double)nQ * (double)nC, algBytes));
-    HIPCK(c, hipEventRecord(e0, s));
-    // (lanesOnly: many queries against a HANDFUL of candidates -- the columns a placement changed, for every sample still waiting,
-    // placement_host.h: the LDS kernel would be one workgroup with a few lanes of each wavefront at work)
-    if (!lanesOnly && (chunkTab || nQ >= 32)) {
-        // enough queries to reuse a staged candidate chunk: the LDS kernel, one workgroup of 16 wavefronts per CU
-        const long long units = (long long)(chunkTab ? nChunkTab : (nC + 63) / 64) * ((nQ + MAPLE_LDS_QB - 1) / MAPLE_LDS_QB);
-        const int gridL = units < 256 ? (int)units : 256;
-        const bool rv_ = c->dm.useRateVariation;
-        const size_t dyn = rv_ ? lds_kernel_dyn_bytes<true>() : lds_kernel_dyn_bytes<false>();
-        static bool attrSet = false;
-        if (!attrSet) {                                                // more than 64 KB of LDS per workgroup has to be asked for
-#define MAPLE_SET_LDS(RV_, U_, SS_) HIPCK(c, hipFuncSetAttribute((const void *)k_append_queries_lds<RV_, U_, SS_>, \
-                                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_kernel_dyn_bytes<RV_>()))
-            MAPLE_SET_LDS(false, false, false); MAPLE_SET_LDS(true, false, false); MAPLE_SET_LDS(false, true, false);
-            MAPLE_SET_LDS(false, true, true); MAPLE_SET_LDS(true, true, false); MAPLE_SET_LDS(true, true, true);
-#undef MAPLE_SET_LDS
-            attrSet = true;
-        }
-        DISPATCH3(c, k_append_queries_lds, <<<gridL, MAPLE_LDS_BLOCK, dyn, s>>>(c->d_model, view(c), nQ, qList, nC, cand, isTip, bLen, out,
-                                                                              ldOut, outCol, qTip, qBLen, counter, tileBest, visitRank,
-                                                                              chunkTab, nChunkTab, nF, finMask));
-    } else
-    DISPATCH3(c, k_append_queries, <<<grid, MAPLE_BLOCK, 0, s>>>(c->d_model, view(c), nQ, qList, nC, cand, isTip, bLen, out, ldOut,
-                                                                  outCol, qTip, qBLen, counter, tileBest, visitRank, finMask));
-    HIPCK(c, hipGetLastError());
-    HIPCK(c, hipEventRecord(e1, s));
-    return MAPLE_OK;
-}
 
 extern "C" int maple_append_batch_dev(maple_ctx *c, int32_t n, const int32_t *pl, const int32_t *cl, const uint8_t *tip,
                                       const double *bl, double *out, void *stream)
@@ -2039,38 +1604,6 @@ extern "C" int maple_append_batch_dev(maple_ctx *c, int32_t n, const int32_t *pl
     return MAPLE_OK;
 }
 
-extern "C" int maple_append_queries_dev(maple_ctx *c, int32_t nQ, const int32_t *qList_dev, int32_t nC,
-                                        const int32_t *cand_dev, int isTipC, double bLen, double *out_dev, void *stream)
-{
-    if (!c || nQ < 0 || nC < 0 || !qList_dev || !cand_dev || !out_dev) return MAPLE_ERR_ARG;
-    if (nQ == 0 || nC == 0) return MAPLE_OK;
-    HIPCK(c, hipSetDevice(c->device));
-    TRY(need_model(c));
-    TRY(settle(c));
-    return launch_append_queries(c, (hipStream_t)stream, nQ, qList_dev, nC, cand_dev, isTipC, bLen, out_dev,
-                                 nC, nullptr, nullptr, nullptr, MAPLE_K_APPEND_QUERIES, 0.0);
-}
-
-// Q queries x C candidates without the score matrix: per query the best score and the candidate that has it (exact
-// ties to the smallest visitRank, or to the smallest index when visitRank is NULL).
-extern "C" int maple_append_queries_argmax_dev(maple_ctx *c, int32_t nQ, const int32_t *qList_dev, int32_t nC,
-                                               const int32_t *cand_dev, const int32_t *visitRank_dev, int isTipC, double bLen,
-                                               double *bestScore_dev, int32_t *bestIdx_dev, void *stream)
-{
-    if (!c || nQ < 0 || nC < 0 || !qList_dev || !cand_dev || !bestScore_dev || !bestIdx_dev) return MAPLE_ERR_ARG;
-    if (nQ == 0 || nC == 0) return MAPLE_OK;
-    HIPCK(c, hipSetDevice(c->device));
-    TRY(need_model(c));
-    TRY(settle(c));
-    const int nChunks = (nC + 63) / 64;
-    HIPCK(c, c->s_tilebest.reserve((size_t)nQ * nChunks * sizeof(TileBest)));
-    TileBest *tb = (TileBest *)c->s_tilebest.p;
-    TRY(launch_append_queries(c, (hipStream_t)stream, nQ, qList_dev, nC, cand_dev, isTipC, bLen, nullptr, 0, nullptr, nullptr, nullptr,
-                              MAPLE_K_APPEND_QUERIES, 0.0, tb, visitRank_dev));
-    hipLaunchKernelGGL(k_argmax_reduce, dim3(nQ), dim3(64), 0, (hipStream_t)stream, nQ, nChunks, tb, bestScore_dev, bestIdx_dev);
-    HIPCK(c, hipGetLastError());
-    return MAPLE_OK;
-}
 
 // ---- RCCL: the arg-max over the ranks' candidate shards (SURVEY 8b / 8e level 2) -----------------------------------------
 // RCCL is loaded at run time (dlopen: the copy the process already has, e.g. PyTorch's, is reused), so the library itself
@@ -2177,221 +1710,6 @@ extern "C" int maple_argmax_allreduce_dev(maple_ctx *c, int32_t n, double *score
     return MAPLE_OK;
 }
 
-#include "placement_host.h"
-#include "update_host.h"
-#include "rebuild_host.h"
-
-// appendProbNode by a whole wavefront per pair (wave_dev.h), small batches of maple_append_batch; the hook of the parity tests is below
-template <bool RV, bool U, bool SS>
-__global__ __launch_bounds__(64) void k_wave_append(const DevModel *__restrict__ mp, ArenaView av, int n, const int32_t *pl,
-                                                    const int32_t *cl, const uint8_t *tip, const double *bl, double *out)
-{
-    __shared__ Lds lds;
-    __shared__ WaveLds wl;
-    const DevModel &m = *mp;
-    stage_model(m, lds);
-    Ctx<RV, U, SS> c(m, lds);
-    for (int i = blockIdx.x; i < n; i += gridDim.x) {
-        const double v = wave_append(c, list_ref(av, pl[i]), av.n_ent[pl[i]], list_ref(av, cl[i]), av.n_ent[cl[i]], tip[i] != 0, bl[i], wl);
-        if (threadIdx.x == 0) out[i] = v;
-        __builtin_amdgcn_wave_barrier();
-    }
-}
-
-#ifdef MAPLE_DEBUG_ABI                                                   // (libmaple_hip_debug.so: include/maple_hip_debug.h)
-// Calibration of the FETCH_SIZE counter for THIS library's access pattern (MI355X_MICROARCH.md, HBM section: the
-// counter is only calibrated for 16 B/lane coalesced streams).  Every lane walks its own contiguous 512-byte "list"
-// with dependent 8-byte loads, exactly like a genome-list walk, over a buffer far larger than the 256 MiB Infinity
-// Cache; the byte count is known, so FETCH_SIZE / bytes is the correction factor for k_append*.
-__global__ __launch_bounds__(MAPLE_BLOCK) void k_calib_walk(const unsigned long long *buf, long long nLists, unsigned long long *sink)
-{
-    unsigned long long acc = 0;
-    for (long long l = (long long)blockIdx.x * blockDim.x + threadIdx.x; l < nLists; l += (long long)gridDim.x * blockDim.x) {
-        const unsigned long long *p = buf + l * 64;
-        unsigned idx = 0;
-        for (int k = 0; k < 64; k++) {
-            unsigned long long w = p[idx];
-            acc += w;
-            idx = (idx + 1 + (unsigned)(w & 0)) & 63;                    // data-dependent next index, like a cursor
-        }
-    }
-    if (acc == 0x123456789abcdefull) *sink = acc;
-}
-
-// WRITE_SIZE calibration: mode 1 writes `bytes` as a coalesced 8-byte-per-lane stream, mode 2 writes ONE 8-byte value into
-// every 64-byte line of the buffer (the score-matrix pattern of k_append_queries: a lane's score lands in a line of its own)
-__global__ __launch_bounds__(MAPLE_BLOCK) void k_calib_write(unsigned long long *buf, long long nWords, int strideWords)
-{
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i * strideWords < nWords; i += (long long)gridDim.x * blockDim.x)
-        buf[i * strideWords] = (unsigned long long)i;
-}
-
-extern "C" int maple_debug_calib_write(maple_ctx *c, uint64_t bytes, int32_t mode, int32_t repeats, float *ms)
-{
-    if (!c || bytes < 512 || repeats <= 0 || mode < 1 || mode > 2) return MAPLE_ERR_ARG;
-    HIPCK(c, hipSetDevice(c->device));
-    unsigned long long *buf = nullptr;
-    HIPCK(c, hipMalloc((void **)&buf, bytes));
-    HIPCK(c, hipMemset(buf, 0, bytes));
-    HIPCK(c, hipDeviceSynchronize());
-    hipEvent_t e0, e1;
-    HIPCK(c, hipEventCreate(&e0));
-    HIPCK(c, hipEventCreate(&e1));
-    HIPCK(c, hipEventRecord(e0, c->stream));
-    for (int r = 0; r < repeats; r++)
-        hipLaunchKernelGGL(k_calib_write, dim3(4096), dim3(MAPLE_BLOCK), 0, c->stream, buf, (long long)(bytes / 8), mode == 1 ? 1 : 8);
-    HIPCK(c, hipEventRecord(e1, c->stream));
-    HIPCK(c, hipEventSynchronize(e1));
-    if (ms) HIPCK(c, hipEventElapsedTime(ms, e0, e1));
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    (void)hipFree(buf);
-    return MAPLE_OK;
-}
-
-extern "C" int maple_debug_calib_walk(maple_ctx *c, uint64_t bytes, int32_t repeats, float *ms)
-{
-    if (!c || bytes < 512 || repeats <= 0) return MAPLE_ERR_ARG;
-    HIPCK(c, hipSetDevice(c->device));
-    unsigned long long *buf = nullptr, *sink = nullptr;
-    HIPCK(c, hipMalloc((void **)&buf, bytes));
-    HIPCK(c, hipMalloc((void **)&sink, 8));
-    HIPCK(c, hipMemset(buf, 1, bytes));
-    HIPCK(c, hipDeviceSynchronize());
-    hipEvent_t e0, e1;
-    HIPCK(c, hipEventCreate(&e0));
-    HIPCK(c, hipEventCreate(&e1));
-    HIPCK(c, hipEventRecord(e0, c->stream));
-    for (int r = 0; r < repeats; r++)
-        hipLaunchKernelGGL(k_calib_walk, dim3(2048), dim3(MAPLE_BLOCK), 0, c->stream, buf, (long long)(bytes / 512), sink);
-    HIPCK(c, hipEventRecord(e1, c->stream));
-    HIPCK(c, hipEventSynchronize(e1));
-    if (ms) HIPCK(c, hipEventElapsedTime(ms, e0, e1));
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    (void)hipFree(buf); (void)hipFree(sink);
-    return MAPLE_OK;
-}
-
-// Parity hooks for the two innermost device functions, which no batched operator exposes on their own: getPartialVec
-// (M:4073-4141) with the caller's matrix (the reference passes mutMatrices[pos] = Q * siteRates[pos]) and simplify
-// (M:3697-3717).  One lane per call.
-struct MatCtx {                        // what gpv_vec / gpv_nuc need from a context: q(r, i, j) of THIS call's matrix
-    const double *M;
-    __device__ inline double q(double, int i, int j) const { return M[i * 4 + j]; }
-};
-struct ThrCtx { struct { double thresholdProb, thresholdProb4; } m; };
-
-__global__ __launch_bounds__(MAPLE_BLOCK) void k_debug_gpv(int n, int usingErrorRate, const int32_t *i12, const double *totLen,
-                                                           const double *M16, const double *errorRate, const double *vect,
-                                                           const uint8_t *upNode, const uint8_t *flag, double *out)
-{
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-        MatCtx c{M16 + 16 * (size_t)i};
-        double o[4];
-        if (i12[i] == 6) gpv_vec(c, 1.0, vect + 4 * (size_t)i, totLen[i], upNode[i] != 0, o);
-        else if (usingErrorRate) gpv_nuc<MatCtx, true>(c, 1.0, i12[i], totLen[i], errorRate[i], upNode[i] != 0, flag[i] != 0, o);
-        else gpv_nuc<MatCtx, false>(c, 1.0, i12[i], totLen[i], errorRate[i], upNode[i] != 0, false, o);
-        for (int k = 0; k < 4; k++) out[4 * (size_t)i + k] = o[k];
-    }
-}
-
-__global__ __launch_bounds__(MAPLE_BLOCK) void k_debug_simplify(int n, double thresholdProb, double thresholdProb4, const double *vec,
-                                                                const int32_t *refA, int32_t *out)
-{
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-        ThrCtx c;
-        c.m.thresholdProb = thresholdProb; c.m.thresholdProb4 = thresholdProb4;
-        out[i] = simplify(c, vec + 4 * (size_t)i, refA[i]);
-    }
-}
-
-extern "C" int maple_debug_gpv_batch(maple_ctx *c, int32_t n, const int32_t *i12, const double *totLen, const double *M16,
-                                     const double *errorRate, const double *vect4, const uint8_t *upNode, const uint8_t *flag,
-                                     double *out4)
-{
-    if (!c || n < 0 || !i12 || !totLen || !M16 || !errorRate || !vect4 || !upNode || !flag || !out4) return MAPLE_ERR_ARG;
-    if (n == 0) return MAPLE_OK;
-    HIPCK(c, hipSetDevice(c->device));
-    TRY(need_model(c));
-    TRY(h2d(c, c->s_i32[0], i12, (size_t)n));
-    TRY(h2d(c, c->s_f64[0], totLen, (size_t)n));
-    TRY(h2d(c, c->s_f64[1], M16, (size_t)16 * n));
-    TRY(h2d(c, c->s_f64[2], errorRate, (size_t)n));
-    TRY(h2d(c, c->s_f64[3], vect4, (size_t)4 * n));
-    TRY(h2d(c, c->s_u8[0], upNode, (size_t)n));
-    TRY(h2d(c, c->s_u8[1], flag, (size_t)n));
-    HIPCK(c, c->s_aux.reserve((size_t)4 * n));
-    hipLaunchKernelGGL(k_debug_gpv, dim3(grid_for(n)), dim3(MAPLE_BLOCK), 0, c->stream, n, c->dm.usingErrorRate, c->s_i32[0].p,
-                       c->s_f64[0].p, c->s_f64[1].p, c->s_f64[2].p, c->s_f64[3].p, c->s_u8[0].p, c->s_u8[1].p, c->s_aux.p);
-    HIPCK(c, hipGetLastError());
-    HIPCK(c, hipMemcpyAsync(out4, c->s_aux.p, (size_t)4 * n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCK(c, hipStreamSynchronize(c->stream));
-    return MAPLE_OK;
-}
-
-extern "C" int maple_debug_simplify_batch(maple_ctx *c, int32_t n, const double *vec4, const int32_t *refA, int32_t *out)
-{
-    if (!c || n < 0 || !vec4 || !refA || !out) return MAPLE_ERR_ARG;
-    if (n == 0) return MAPLE_OK;
-    HIPCK(c, hipSetDevice(c->device));
-    TRY(h2d(c, c->s_f64[0], vec4, (size_t)4 * n));
-    TRY(h2d(c, c->s_i32[0], refA, (size_t)n));
-    HIPCK(c, c->s_i32[1].reserve(n));
-    hipLaunchKernelGGL(k_debug_simplify, dim3(grid_for(n)), dim3(MAPLE_BLOCK), 0, c->stream, n, c->dm.thresholdProb,
-                       c->dm.thresholdProb4, c->s_f64[0].p, c->s_i32[0].p, c->s_i32[1].p);
-    HIPCK(c, hipGetLastError());
-    HIPCK(c, hipMemcpyAsync(out, c->s_i32[1].p, n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    HIPCK(c, hipStreamSynchronize(c->stream));
-    return MAPLE_OK;
-}
-
-// debugging aid: record the visit sequence (t1, direction, needsUpdating, failedPasses, lastLK, midProb) of one query
-extern "C" int maple_debug_wave_append_batch(maple_ctx *c, int32_t n, const int32_t *pl, const int32_t *cl, const uint8_t *tip,
-                                             const double *bl, double *out, float *ms)
-{
-    if (!c || n < 0 || !pl || !cl || !tip || !bl || !out) return MAPLE_ERR_ARG;
-    if (n == 0) return MAPLE_OK;
-    HIPCK(c, hipSetDevice(c->device));
-    TRY(need_model(c));
-    TRY(check_ids(c, n, pl, false, "parentList"));
-    TRY(check_ids(c, n, cl, false, "childList"));
-    TRY(stage_begin(c, (size_t)n * 32 + 256));
-    STAGE(dpl, c, pl, n); STAGE(dcl, c, cl, n); STAGE(dtip, c, tip, n); STAGE(dbl, c, bl, n);
-    TRY(stage_flush(c));
-    HIPCK(c, c->s_f64[1].reserve(n));
-    hipEvent_t e0, e1;
-    TRY(ev_pair(c, &e0, &e1, MAPLE_K_OTHER, (double)n, 0.0));
-    HIPCK(c, hipEventRecord(e0, c->stream));
-    DISPATCH3(c, k_wave_append, <<<std::min(n, 256 * 16), 64, 0, c->stream>>>(c->d_model, view(c), n, dpl, dcl, dtip, dbl, c->s_f64[1].p));
-    HIPCK(c, hipGetLastError());
-    HIPCK(c, hipEventRecord(e1, c->stream));
-    HIPCK(c, hipMemcpyAsync(out, c->s_f64[1].p, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCK(c, hipStreamSynchronize(c->stream));
-    if (ms) HIPCK(c, hipEventElapsedTime(ms, e0, e1));
-    return MAPLE_OK;
-}
-
-extern "C" int maple_debug_trace_query(maple_ctx *c, int32_t query)
-{
-    if (!c) return MAPLE_ERR_ARG;
-    c->trace_query = query;
-    if (query >= 0) {
-        HIPCK(c, c->s_trace_i.reserve(4 * 4096 + 4));
-        HIPCK(c, c->s_trace_d.reserve(2 * 4096));
-        HIPCK(c, hipMemset(c->s_trace_i.p, 0, (4 * 4096 + 4) * sizeof(int32_t)));
-    }
-    return MAPLE_OK;
-}
-
-extern "C" int maple_debug_trace_read(maple_ctx *c, int32_t *n, int32_t *items4, double *vals2)
-{
-    if (!c || !n || !items4 || !vals2 || !c->s_trace_i.p) return MAPLE_ERR_ARG;
-    HIPCK(c, hipMemcpy(n, c->s_trace_i.p + 4 * 4096, sizeof(int32_t), hipMemcpyDeviceToHost));
-    HIPCK(c, hipMemcpy(items4, c->s_trace_i.p, 4 * 4096 * sizeof(int32_t), hipMemcpyDeviceToHost));
-    HIPCK(c, hipMemcpy(vals2, c->s_trace_d.p, 2 * 4096 * sizeof(double), hipMemcpyDeviceToHost));
-    return MAPLE_OK;
-}
-
-#endif  // MAPLE_DEBUG_ABI
 
 extern "C" int maple_timing_reset(maple_ctx *c)
 {

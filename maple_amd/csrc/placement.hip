@@ -1,11 +1,38 @@
-// maple_placement_search_batch: findBestParentForNewSample (MAPLEv0.7.5.4.py:7912-8292) for MANY query samples on one
-// frozen tree (the shape of --findSamplePlacements / --lineageRefs, M:11190-11220, and of online batches).
-// Included by maple_hip.hip ahead of the tree-mirror section; composes the library's own batch entry points plus three kernels:
+// maple_amd/csrc/placement.hip -- maple_placement_search_batch: findBestParentForNewSample (MAPLEv0.7.5.4.py:7912-8292) for
+// MANY query samples on one frozen tree (the shape of --findSamplePlacements / --lineageRefs, M:11190-11220, and of online
+// batches).
+// A translation unit of libmaple_hip.so (gfx950 only); composes the library's own batch entry points plus three kernels:
 //   k_place_score  - every query against every candidate branch, each in the candidate's MAT reference frame
 //   k_place_minor  - isMinorSequence of every query against every leaf
 //   k_place_replay - the reference's depth-first traversal over those scores, one lane per query (a forward scan of the tree
 //                    laid out in traversal order)
-#pragma once
+#include "../../include/maple_hip.h"
+#include "genome_dev.h"
+#include "search_dev.h"
+#include "placement_dev.h"
+#include "ctx_host.h"
+#include "batch_host.h"
+
+#include <algorithm>
+#include <chrono>
+#include <cmath>
+#include <cstring>
+#include <thread>
+#include <vector>
+
+namespace maple {
+static __global__ __launch_bounds__(64) void k_place_replay(const ScanRec *__restrict__ R, int nReach, PlaceParams P, int nQ, int nCols,
+                                                     int rootCol, const double *__restrict__ score, int nLeaf,
+                                                     const uint8_t *__restrict__ minor, const int32_t *__restrict__ frameOf,
+                                                     int nF, int stateCap, double *stLK, int16_t *stFails, uint32_t *frameBits,
+                                                     PlaceOut o)
+{
+    const int q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= nQ) return;
+    place_replay_one(R, nReach, P, q, nQ, score + (long long)q * nCols, rootCol, minor + (long long)q * nLeaf, frameOf, nF,
+                     stateCap, stLK, stFails, frameBits, o);
+}
+}  // namespace maple
 
 // same scheduling as k_append_queries (dynamic 64-candidate tiles per wavefront, candidate-chunk-major, candidates sorted by
 // list length), with the query taken in each candidate's MAT reference frame

@@ -350,7 +350,7 @@ def update_genome_lists(dev: Device, tree: HostTree, changed, changed_dist=None,
     branches re-estimates the branch above the changed child like updateBLen (M:5385-5414).
     ``tree.id_*`` and ``tree.dist`` are updated in place; returns the number of lists replaced.
 
-    ``native`` (default): the level loop runs inside the library (maple_update_partials, maple_amd/csrc/update_host.h) on
+    ``native`` (default): the level loop runs inside the library (maple_update_partials, maple_amd/csrc/update.hip) on
     these same columns; the Python loop below is the same algorithm call for call and is kept as its cross-check."""
     if native and changed_dist is None:
         up_, c0_, c1_, tip_, depth_ = tree.columns()

@@ -24,8 +24,8 @@ STD_MODES = le.MODES[:5]
 
 
 def kernel_constant(name):
-    """A #define of maple_amd/csrc/maple_hip.hip: the routes of the dense kernel follow the constants the library is built with."""
-    with open(os.path.join(ROOT, "maple_amd", "csrc", "maple_hip.hip")) as fh:
+    """A #define of maple_amd/csrc/append_queries.hip: the routes of the dense kernel follow the constants the library is built with."""
+    with open(os.path.join(ROOT, "maple_amd", "csrc", "append_queries.hip")) as fh:
         return int(re.search(rf"#define {name} (\d+)", fh.read()).group(1))
 
 
@@ -206,7 +206,7 @@ def test_evaluatePlacement_every_form(ctx, mode):
 
 
 def dense_routes(dev, q_ids, c_ids):
-    """Which route of k_append_queries_lds each chunk and query takes (maple_hip.hip: a chunk of 64 candidates is staged in
+    """Which route of k_append_queries_lds each chunk and query takes (append_queries.hip: a chunk of 64 candidates is staged in
     LDS if its words fit MAPLE_LDS_CAPW and its aux doubles MAPLE_LDS_CAPA; a query if it has <= MAPLE_QLDS entries)."""
     capw, capa, qlds, qb = (kernel_constant(x) for x in ("MAPLE_LDS_CAPW", "MAPLE_LDS_CAPA", "MAPLE_QLDS", "MAPLE_LDS_QB"))
     ne_c, na_c = dev.sizes(c_ids)

@@ -534,7 +534,7 @@ def test_update_partials_matches_reference(uname):
             twin_replaced = update_genome_lists(dev, twin, [v], native=False)
         except RuntimeError as e:
             # the Python cross-check stops where the upper pass meets an inconsistent zero-length branch (the reference's
-            # updateBLen inside the from-parent direction, M:5522-5600); the library's loop handles it (update_host.h) and is
+            # updateBLen inside the from-parent direction, M:5522-5600); the library's loop handles it (update.hip) and is
             # still compared with the reference's own repair below
             if "updateBLen" not in str(e):
                 raise
