@@ -1,8 +1,9 @@
 // maple_amd/csrc/batch_host.h -- the small host-side helpers every translation unit with batch entry points shares (each gets its
-// own copy: they only touch the context): launch geometry, the dispatch over the three model switches, list-id checks, the
-// staging arena for a call's arguments, event pairs; the launch attributes the scoring kernels share; and the declarations of the
-// host functions that cross translation units (hidden visibility: not part of the C ABI).  Included by every unit with batch
-// entry points: maple_hip.hip, append_queries.hip, placement.hip, update.hip, spr_batch.hip, debug_abi.hip.
+// own copy: they only touch the context): launch geometry, list-id checks, the staging arena for a call's arguments, event pairs;
+// the launch attributes the scoring kernels share; and the declarations of the host functions that cross translation units
+// (hidden visibility: not part of the C ABI).  The dispatch over the three model switches, DISPATCH3, is in ctx_host.h.
+// Included by every unit with batch entry points: maple_hip.hip, append_queries.hip, placement.hip, update.hip, spr_batch.hip,
+// debug_abi.hip.
 #pragma once
 #include "ctx_host.h"
 
@@ -33,17 +34,6 @@ static int grid_for(int n)
     if (g > 256 * 8) g = 256 * 8;      // 256 CUs x 8 workgroups, grid-stride beyond
     return g;
 }
-
-#define DISPATCH3(c, KERNEL, ...)                                                                          \
-    do {                                                                                                  \
-        const bool rv_ = (c)->dm.useRateVariation, u_ = (c)->dm.usingErrorRate, ss_ = (c)->dm.errorRateSiteSpecific; \
-        if (!rv_ && !u_) KERNEL<false, false, false> __VA_ARGS__;                                          \
-        else if (rv_ && !u_) KERNEL<true, false, false> __VA_ARGS__;                                       \
-        else if (!rv_ && u_ && !ss_) KERNEL<false, true, false> __VA_ARGS__;                               \
-        else if (!rv_ && u_ && ss_) KERNEL<false, true, true> __VA_ARGS__;                                 \
-        else if (rv_ && u_ && !ss_) KERNEL<true, true, false> __VA_ARGS__;                                 \
-        else KERNEL<true, true, true> __VA_ARGS__;                                                         \
-    } while (0)
 
 
 static int check_ids(maple_ctx *c, int32_t n, const int32_t *ids, bool allowNeg, const char *what)

@@ -339,6 +339,19 @@ static inline int wave_item_max(const maple_ctx *c, int dflt)
 
 #define TRY(x) do { int rc_ = (x); if (rc_) return rc_; } while (0)
 
+// the three model switches of the context pick the instance of a kernel template <bool RV, bool U, bool SS>:
+// DISPATCH3(c, k_name, <<<grid, block, lds, stream>>>(args...))
+#define DISPATCH3(c, KERNEL, ...)                                                                          \
+    do {                                                                                                  \
+        const bool rv_ = (c)->dm.useRateVariation, u_ = (c)->dm.usingErrorRate, ss_ = (c)->dm.errorRateSiteSpecific; \
+        if (!rv_ && !u_) KERNEL<false, false, false> __VA_ARGS__;                                          \
+        else if (rv_ && !u_) KERNEL<true, false, false> __VA_ARGS__;                                       \
+        else if (!rv_ && u_ && !ss_) KERNEL<false, true, false> __VA_ARGS__;                               \
+        else if (!rv_ && u_ && ss_) KERNEL<false, true, true> __VA_ARGS__;                                 \
+        else if (rv_ && u_ && !ss_) KERNEL<true, true, false> __VA_ARGS__;                                 \
+        else KERNEL<true, true, true> __VA_ARGS__;                                                         \
+    } while (0)
+
 // one (start, stop) pair of HIP events from the context's pool, tagged with the kind of launch it brackets and the work it
 // did (maple_timing_read_kind); defined in maple_hip.hip
 __attribute__((visibility("hidden")))

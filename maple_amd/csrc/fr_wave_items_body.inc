@@ -1,53 +1,22 @@
-// maple_amd/csrc/frontier_upd_wave.inc -- one list-updating item of the frontier tier by a whole WAVEFRONT, for one size class of
-// lists.  The including translation unit defines, before wave_dev.h / wave_update.h: MAPLE_WU_IN (entries per staged input
-// list) and MAPLE_WAVE_CAPW (entries of the lists appendProbNode stages), and: FRW_KERNEL (the kernel's name), FRW_PERM /
-// FRW_COUNT (the level's list of this class's items in FPools / FCtr, filled by k_fr_sort_level).
-// ---- the same items by a whole wavefront: the few whose lists are long -------------------------------------------------------
-// mergeVectors, areVectorsDifferent and appendProbNode cut along the merge path of the two lists (wave_update.h, wave_dev.h:
-// lane d does step d of the walk; bit for bit the one-lane walks), every list of the item in LDS.  An item with a list beyond
-// the staging limit is walked by lane 0 alone.
-__device__ inline int fstore_wave(const FPools &fp, const unsigned long long *w, const double *a, int n, int na)
-{
-    const int lane = threadIdx.x & 63;
-    unsigned long long id = 0, ow = 0, oa = 0;
-    if (lane == 0) {
-        id = atomicAdd(&fp.ctr->nLists, 1ull);
-        ow = atomicAdd(&fp.ctr->usedW, (unsigned long long)n);
-        oa = atomicAdd(&fp.ctr->usedA, (unsigned long long)na);
-    }
-    auto bc = [](unsigned long long x) {
-        return ((unsigned long long)(uint32_t)__shfl((int)(x >> 32), 0, 64) << 32) | (uint32_t)__shfl((int)x, 0, 64);
-    };
-    id = bc(id); ow = bc(ow); oa = bc(oa);
-    if ((long long)id >= fp.capL || (long long)(ow + n) > fp.capW || (long long)(oa + na) > fp.capA) {
-        if (lane == 0) fp.ctr->overflow = 1;
-        return -2;
-    }
-    unsigned long long *dw = (unsigned long long *)(fp.tw + ow);
-    double *da = fp.ta + oa;
-    for (int k = lane; k < n; k += 64) dw[k] = w[k];
-    for (int k = lane; k < na; k += 64) da[k] = a[k];
-    if (lane == 0) { fp.trec[id] = lrec_make((long long)ow, n, (long long)oa, na); fp.tflag[id] = 0; }
-    __threadfence();
-    wave_sync();
-    return (int)id;
-}
-
-template <bool RV, bool U, bool SS>
-__global__ __launch_bounds__(64) void FRW_KERNEL(const DevModel *__restrict__ mp, ArenaViewS av, DevTree T, SearchParams P, FPools fp,
-                                                         int budget, int heavyMin, long long laneBase)
-{
+// maple_amd/csrc/fr_wave_items_body.inc -- the body of k_fr_updating_wave_s / k_fr_updating_wave: the level's items of one size
+// class, dealt to the wavefronts.  Included as the whole body of a kernel
+//     template <bool RV, bool U, bool SS> __global__ __launch_bounds__(64) void k(const DevModel *__restrict__ mp, ArenaViewS av,
+//         DevTree T, SearchParams P, FPools fp, int budget, int heavyMin, long long laneBase)
+// after `using Class = frt::WaveSmall` or `frt::WaveBig` (as merge_step_body.inc is the body of the walks' steps).  Not a function:
+// a body that is optimised on its own before it is inlined into its kernel compiles to other code -- the inliner then sees the
+// lambdas' captures resolved and takes other decisions (wave_append's append_walk fallback inlined twice, 11 % more code).
     __shared__ Lds lds;
-    __shared__ WaveUpdLds L;
+    __shared__ WaveUpdLds<Class::wuIn> L;
+    typedef WaveLds<Class::capW> WaveLdsC;
     const DevModel &m = *mp;
     stage_model(m, lds);
     Ctx<RV, U, SS> c(m, lds);
     const int lane = threadIdx.x;
-    WaveLds &W = *reinterpret_cast<WaveLds *>(L.baux);                     // (appendProbNode's staging: baux is free by then)
-    static_assert(sizeof(WaveLds) <= sizeof(L.baux), "LDS alias");
+    WaveLdsC &W = *reinterpret_cast<WaveLdsC *>(L.baux);                   // (appendProbNode's staging: baux is free by then)
+    static_assert(sizeof(WaveLdsC) <= sizeof(L.baux), "LDS alias");
     const long long lo = (long long)fp.ctr->loU;
-    // the level's items that go a wavefront each, listed by k_fr_sort_level (perm3): dealt to the wavefronts one at a time
-    const long long nHeavy = (long long)fp.ctr->FRW_COUNT;
+    // the level's items that go a wavefront each, listed by k_fr_sort_level (Class::perm): dealt to the wavefronts one at a time
+    const long long nHeavy = (long long)(fp.ctr->*Class::count);
     (void)heavyMin;
     // (what the launch did, for the roofline of the bench line -- the same account as k_fr_updating's: the two lists every
     // mergeVectors reads and the one it writes; kept by lane 0, one atomic per wavefront at the end)
@@ -56,7 +25,7 @@ __global__ __launch_bounds__(64) void FRW_KERNEL(const DevModel *__restrict__ mp
         nU++;
 #ifdef MAPLE_SPR_PROFILE
         const long long tItem0 = wall_clock64();
-        int profCls = (MAPLE_WU_IN > 128) ? 1 : 0;
+        int profCls = Class::profCls;
         struct ProfEnd {                                                    // (booked on every way out of the item's block)
             const FPools &fp; const long long t0; int &cls;
             __device__ ~ProfEnd() {
@@ -68,7 +37,7 @@ __global__ __launch_bounds__(64) void FRW_KERNEL(const DevModel *__restrict__ mp
         } profEnd{fp, tItem0, profCls};
 #endif
         {
-            const long long i = lo + fp.FRW_PERM[kk];
+            const long long i = lo + (fp.*Class::perm)[kk];
             FItem &it = fp.U[i];
             FSearch &S = fp.S[it.q];
             if (!fs_live(S.state)) { if (lane == 0) it.flags |= FI_DEAD; continue; }
@@ -83,7 +52,7 @@ __global__ __launch_bounds__(64) void FRW_KERNEL(const DevModel *__restrict__ mp
             // every list the item touches must fit the staging areas; else lane 0 walks the item alone
             const FList lp = fvalid(hPassed) ? flist(av, fp, hPassed) : FList{nullptr, nullptr, 0, 0};
             const FList lr = flist(av, fp, hRpr);
-            const bool fits = fr_wave_fits(av, T, fp, it, MAPLE_WU_IN, MAPLE_WAVE_CAPW);
+            const bool fits = fr_wave_fits(av, T, fp, it, Class::wuIn, Class::capW);
             if (!fits) {
 #ifdef MAPLE_SPR_PROFILE
                 profCls += 2;
@@ -98,7 +67,7 @@ __global__ __launch_bounds__(64) void FRW_KERNEL(const DevModel *__restrict__ mp
             int nM = 0, naM = 0;
             // mergeVectors into L.m / L.maux: 0 ok, -1 None, -2 fatal
             auto merge = [&](const FList &l1, double b1, bool tp1, const FList &l2, double b2, bool tp2, bool upDown) -> int {
-                if (l1.n > MAPLE_WU_IN || l2.n > MAPLE_WU_IN) return -2;     // (a list that grew beyond the staging on its way through a reference branch)
+                if (l1.n > L.wuIn || l2.n > L.wuIn) return -2;               // (a list that grew beyond the staging on its way through a reference branch)
                 wave_sync();
                 const int r = wave_merge(c, fref(l1), l1.n, b1, tp1, fref(l2), l2.n, b2, tp2, upDown, L, naM);
                 bU += 8ull * (unsigned long long)(l1.n + l1.na + l2.n + l2.na + (r > 0 ? r + naM : 0));
@@ -277,4 +246,3 @@ __global__ __launch_bounds__(64) void FRW_KERNEL(const DevModel *__restrict__ mp
         }
     }
     if (lane == 0 && nU) { atomicAdd(&fp.ctr->itemsU, nU); atomicAdd(&fp.ctr->bytesU, bU); }
-}

@@ -290,8 +290,8 @@ __global__ __launch_bounds__(FR_BLOCK) void k_fr_sort_level(ArenaViewS av, DevTr
                 // a list beyond the 512-entry staging -- would be walked by lane 0 of a wavefront of the 512 class, of which there
                 // is one per compute unit: 0.3-1.7 ms each, one after the other (a level of 32 000 items by wavefronts: 10.5 ms,
                 // 8 of them for its 2 800 such items).  They stay one-lane items, 16 to a wavefront, next to each other.
-                small = fr_wave_fits(av, T, fp, it, FR_WAVE_SMALL_IN, FR_WAVE_SMALL_CAPW);
-                if (!small && !fr_wave_fits(av, T, fp, it, 512, 512)) kind = (it.dir == 0 ? 2 : 3);
+                small = fr_wave_fits(av, T, fp, it, WaveSmall::wuIn, WaveSmall::capW);
+                if (!small && !fr_wave_fits(av, T, fp, it, WaveBig::wuIn, WaveBig::capW)) kind = (it.dir == 0 ? 2 : 3);
             }
         }
         const unsigned long long below = (1ull << lane) - 1ull;
@@ -1350,7 +1350,7 @@ int frontier_search(maple_ctx *c, const SearchParams &P, int m, const int32_t *n
         HIPCK(c, hipGetLastError());
     }
     // (the seeding of a tree with local references writes lists through the lanes' scratch slabs: no more lanes than slabs)
-    FR_DISPATCH3(c, k_fr_begin, <<<std::min(gridN, gridUpd), FR_BLOCK, 0, s>>>(c->d_model, av, T, P, m, F.nodes.p, fp, dout, budget, zeroBudget,
+    DISPATCH3(c, k_fr_begin, <<<std::min(gridN, gridUpd), FR_BLOCK, 0, s>>>(c->d_model, av, T, P, m, F.nodes.p, fp, dout, budget, zeroBudget,
                                                             anyWide ? F.wideRow.p : nullptr, anyWide ? wide->forceWide : 0,
                                                             overHint ? F.overHint.p : nullptr));
     HIPCK(c, hipGetLastError());
@@ -1363,8 +1363,9 @@ int frontier_search(maple_ctx *c, const SearchParams &P, int m, const int32_t *n
     // (a launch of 16 384 workgroups costs 0.4-0.5 ms even when it finds ten thousand items: the grid goes with the batch -- a
     // round's largest launch holds ~21 items per search)
     const int gridCached = (int)std::min<long long>(16384, std::max<long long>(512, (long long)m / 12));
-    // items whose two lists add up to this many entries are walked by a wavefront each (k_fr_updating_wave: 54 KB of LDS per
-    // wavefront, two per compute unit)
+    // items whose two lists add up to this many entries are walked by a wavefront each, in two size classes (frontier_dev.h):
+    // k_fr_updating_wave_s, sizeof(WaveUpdLds<128>) = 27 680 bytes of LDS per wavefront, five wavefronts per compute unit, and
+    // k_fr_updating_wave, sizeof(WaveUpdLds<512>) = 110 720 bytes, one per compute unit (+ 160 bytes of model constants each)
     // (a handful of searches -- the re-search of a proposed move -- wait for every single item: all of them by wavefronts)
     const int heavyMin = m <= 64 ? 1 : std::max(256, FR_HEAVY_MULT * (int)meanEnt / 4), gridWave = 256, gridWaveSmall = 1280;
     const int bigMin = m <= 64 ? (1 << 30) : FR_BIG_MIN;                  // (lists of this many entries together: 16 items to a wavefront)
@@ -1432,13 +1433,13 @@ int frontier_search(maple_ctx *c, const SearchParams &P, int m, const int32_t *n
             // k_fr_cached, on a stream of their own: the launch scores every other item, these are the next launch's
             HIPCK(c, hipEventRecord(F.evFork2, s2));
             HIPCK(c, hipStreamWaitEvent(s3, F.evFork2, 0));
-            FR_DISPATCH3(c, k_fr_pass_wave, <<<1024, FR_BLOCK, 0, s3>>>(c->d_model, av, T, fp));
-            FR_DISPATCH3(c, k_fr_pass, <<<256, FR_BLOCK, 0, s3>>>(c->d_model, av, T, fpC, scratchLanes + 2048));
+            DISPATCH3(c, k_fr_pass_wave, <<<1024, FR_BLOCK, 0, s3>>>(c->d_model, av, T, fp));
+            DISPATCH3(c, k_fr_pass, <<<256, FR_BLOCK, 0, s3>>>(c->d_model, av, T, fpC, scratchLanes + 2048));
             HIPCK(c, hipEventRecord(F.evJoin2, s3));
             passQueued = true;
             TRY(stage("k_fr_pass"));
         }
-        FR_DISPATCH3(c, k_fr_cached, <<<gridCached, FR_BLOCK, 0, s2>>>(c->d_model, av, anyWide ? Tw : T, P, fp, budget,
+        DISPATCH3(c, k_fr_cached, <<<gridCached, FR_BLOCK, 0, s2>>>(c->d_model, av, anyWide ? Tw : T, P, fp, budget,
                                                                         anyWide ? F.wideRow.p : nullptr,
                                                                         anyWide ? wide->fin : FiniteRows{nullptr, nullptr, 0}));
         HIPCK(c, hipEventRecord(b1, s2));
@@ -1524,10 +1525,10 @@ int frontier_search(maple_ctx *c, const SearchParams &P, int m, const int32_t *n
     TRY(stage("k_fr_replay"));
     if (anyWide) HIPCK(c, hipStreamWaitEvent(s, F.evJoin, 0));
     if (anyWide && fp.mat && wide->nFrames > 0) {
-        FR_DISPATCH3(c, k_fr_wide_frames, <<<std::min(gridUpd, 512), FR_BLOCK, 0, s>>>(c->d_model, av, T, fp, wide->frameParent, wide->frameNode));
+        DISPATCH3(c, k_fr_wide_frames, <<<std::min(gridUpd, 512), FR_BLOCK, 0, s>>>(c->d_model, av, T, fp, wide->frameParent, wide->frameNode));
         TRY(stage("k_fr_wide_frames"));
     }
-    FR_DISPATCH3(c, k_fr_refine, <<<gridUpd, FR_BLOCK, 0, s>>>(c->d_model, av, T, fp));
+    DISPATCH3(c, k_fr_refine, <<<gridUpd, FR_BLOCK, 0, s>>>(c->d_model, av, T, fp));
     TRY(stage("k_fr_refine"));
     k_fr_finish<<<gridN, FR_BLOCK, 0, s>>>(av, T, P, m, fp, dout, poolW, poolA, poolUsed, poolCapW, poolCapA);
     HIPCK(c, hipGetLastError());

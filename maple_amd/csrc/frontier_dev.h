@@ -571,8 +571,19 @@ __device__ inline bool fr_wave_fits(const ArenaViewS &av, const DevTree &T, cons
     if (dir != 0 && ids[4] >= 0 && nP + av.n_ent[ids[4]] + gO > wuIn) return false;
     return true;
 }
-#define FR_WAVE_SMALL_IN 128           // the small class of the wavefront-wide items: staging for 128-entry lists (27 KB of LDS per
-#define FR_WAVE_SMALL_CAPW 256         // wavefront, five wavefronts per compute unit); the rest: 512 entries, one per compute unit
+// The two size classes of the wavefront-wide items: what k_fr_sort_level sorts by and the kernels of fr_wave_items_body.inc are
+// compiled for.  wuIn / capW: the staging of WaveUpdLds / WaveLds (wave_update.h, wave_dev.h); perm / count: the level's list of
+// the class's items and their number; profCls: the class's slot of FCtr::dbgW* (MAPLE_SPR_PROFILE).
+struct WaveSmall {                     // 128-entry lists: 27 KB of LDS per wavefront, five wavefronts per compute unit (k_fr_updating_wave_s)
+    static constexpr int wuIn = 128, capW = 256, profCls = 0;
+    static constexpr int32_t *FPools::*perm = &FPools::perm3;
+    static constexpr unsigned long long FCtr::*count = &FCtr::permHeavy;
+};
+struct WaveBig {                       // the rest, up to 512 entries: 108 KB, one wavefront per compute unit (k_fr_updating_wave)
+    static constexpr int wuIn = 512, capW = 512, profCls = 1;
+    static constexpr int32_t *FPools::*perm = &FPools::perm4;
+    static constexpr unsigned long long FCtr::*count = &FCtr::permHeavy2;
+};
 
 // One lane takes milliseconds for an item whatever the GPU is doing, and a level waits for its slowest item: a level with few
 // items -- every level past the first ten, where a few thousand searches near the root are still updating lists -- is walked by
@@ -584,17 +595,6 @@ __device__ __forceinline__ int fr_level_heavy_min(const FPools &fp, int heavyMin
 }
 
 }  // namespace frt
-
-#define FR_DISPATCH3(c, KERNEL, ...)                                                                       \
-    do {                                                                                                  \
-        const bool rv_ = (c)->dm.useRateVariation, u_ = (c)->dm.usingErrorRate, ss_ = (c)->dm.errorRateSiteSpecific; \
-        if (!rv_ && !u_) KERNEL<false, false, false> __VA_ARGS__;                                          \
-        else if (rv_ && !u_) KERNEL<true, false, false> __VA_ARGS__;                                       \
-        else if (!rv_ && u_ && !ss_) KERNEL<false, true, false> __VA_ARGS__;                               \
-        else if (!rv_ && u_ && ss_) KERNEL<false, true, true> __VA_ARGS__;                                 \
-        else if (rv_ && u_ && !ss_) KERNEL<true, true, false> __VA_ARGS__;                                 \
-        else KERNEL<true, true, true> __VA_ARGS__;                                                         \
-    } while (0)
 
 // the level kernels of frontier_upd.hip, queued on stream s (kernels of another translation unit cannot be launched directly)
 __attribute__((visibility("hidden")))

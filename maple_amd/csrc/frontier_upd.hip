@@ -1,19 +1,11 @@
 // maple_amd/csrc/frontier_upd.hip -- frontier tier of the SPR search (see frontier.hip): the kernels of the items that arrive with
 // needsUpdating == True (M:6982-7091, 7182-7304): lists merged along the path, by one lane per item (k_fr_updating) or, for the few
 // with the longest lists, by a wavefront per item (k_fr_updating_wave).
-#include "frontier_dev.h"
-// (this translation unit's wavefront-wide walks serve the FEW items with the longest lists, one wavefront per compute unit:
-// staging areas for lists of 512 entries, 110 KB of LDS)
-#define MAPLE_WAVE_CAPW 512
-#define MAPLE_WU_IN 512
-#include "wave_dev.h"
-#include "wave_update.h"
+#include "frontier_upd_wave.h"
 
 using namespace frt;
 
 namespace {
-
-#include "frontier_upd_lane.inc"
 
 #ifndef FR_UPD_WAVES
 #define FR_UPD_WAVES 4                // wavefronts per SIMD k_fr_updating is compiled for (128 registers, the rest of its state in scratch)
@@ -81,29 +73,27 @@ void k_fr_updating(const DevModel *__restrict__ mp, ArenaViewS av, DevTree T, Se
     if ((threadIdx.x & 63) == 0 && nU) { atomicAdd(&fp.ctr->itemsU, nU); atomicAdd(&fp.ctr->bytesU, bU); }
 }
 
-#define FRW_KERNEL k_fr_updating_wave
-#define FRW_PERM perm4
-#define FRW_COUNT permHeavy2
-#include "frontier_upd_wave.inc"
+// (the wavefront-wide walks of this translation unit serve the FEW items with the longest lists, one wavefront per compute unit:
+// staging areas for lists of 512 entries, 108 KB of LDS)
+template <bool RV, bool U, bool SS>
+__global__ __launch_bounds__(64) void k_fr_updating_wave(const DevModel *__restrict__ mp, ArenaViewS av, DevTree T, SearchParams P, FPools fp,
+                                                         int budget, int heavyMin, long long laneBase)
+{
+    using Class = WaveBig;
+#include "fr_wave_items_body.inc"
+}
+
+// k_fr_updating with its fourth switch bound (does the tree have MAT local references?), for DISPATCH3 over the model's three
+template <bool RV, bool U, bool SS> constexpr auto k_fr_updating_mat = k_fr_updating<RV, U, SS, true>;
+template <bool RV, bool U, bool SS> constexpr auto k_fr_updating_plain = k_fr_updating<RV, U, SS, false>;
 }  // namespace
 
 
 int fr_launch_updating(maple_ctx *c, hipStream_t s, int grid, const ArenaViewS &av, const DevTree &T, const SearchParams &P, const FPools &fp,
                        int budget, int heavyMin)
 {
-    const bool rv_ = c->dm.useRateVariation, u_ = c->dm.usingErrorRate, ss_ = c->dm.errorRateSiteSpecific;
-#define FR_UPD_LAUNCH(RV, U, SS)                                                                                        \
-    do {                                                                                                               \
-        if (fp.mat) k_fr_updating<RV, U, SS, true><<<grid, FR_BLOCK, 0, s>>>(c->d_model, av, T, P, fp, budget, heavyMin); \
-        else k_fr_updating<RV, U, SS, false><<<grid, FR_BLOCK, 0, s>>>(c->d_model, av, T, P, fp, budget, heavyMin);       \
-    } while (0)
-    if (!rv_ && !u_) FR_UPD_LAUNCH(false, false, false);
-    else if (rv_ && !u_) FR_UPD_LAUNCH(true, false, false);
-    else if (!rv_ && u_ && !ss_) FR_UPD_LAUNCH(false, true, false);
-    else if (!rv_ && u_ && ss_) FR_UPD_LAUNCH(false, true, true);
-    else if (rv_ && u_ && !ss_) FR_UPD_LAUNCH(true, true, false);
-    else FR_UPD_LAUNCH(true, true, true);
-#undef FR_UPD_LAUNCH
+    if (fp.mat) DISPATCH3(c, k_fr_updating_mat, <<<grid, FR_BLOCK, 0, s>>>(c->d_model, av, T, P, fp, budget, heavyMin));
+    else DISPATCH3(c, k_fr_updating_plain, <<<grid, FR_BLOCK, 0, s>>>(c->d_model, av, T, P, fp, budget, heavyMin));
     HIPCK(c, hipGetLastError());
     return MAPLE_OK;
 }
@@ -111,7 +101,7 @@ int fr_launch_updating(maple_ctx *c, hipStream_t s, int grid, const ArenaViewS &
 int fr_launch_updating_wave(maple_ctx *c, hipStream_t s, int grid, const ArenaViewS &av, const DevTree &T, const SearchParams &P,
                             const FPools &fp, int budget, int heavyMin, long long laneBase)
 {
-    FR_DISPATCH3(c, k_fr_updating_wave, <<<grid, 64, 0, s>>>(c->d_model, av, T, P, fp, budget, heavyMin, laneBase));
+    DISPATCH3(c, k_fr_updating_wave, <<<grid, 64, 0, s>>>(c->d_model, av, T, P, fp, budget, heavyMin, laneBase));
     HIPCK(c, hipGetLastError());
     return MAPLE_OK;
 }

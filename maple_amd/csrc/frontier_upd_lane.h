@@ -1,5 +1,10 @@
-// maple_amd/csrc/frontier_upd_lane.inc -- one list-updating item of the frontier tier by ONE lane (included by the translation
+// maple_amd/csrc/frontier_upd_lane.h -- one list-updating item of the frontier tier by ONE lane (included by the translation
 // units that hold a k_fr_updating* kernel: a device function cannot be called across translation units)
+#pragma once
+#include "frontier_dev.h"
+
+namespace frt {
+
 // ---- items that arrived with needsUpdating == True (M:6982-7091, 7182-7304): lists merged along the path ----------------
 // (dir 3: the seeding of a search whose pruned node hangs off the root, M:6916-6960 -- two rootVector calls)
 // one such item by one lane (the one-lane list walks of genome_dev.h)
@@ -217,3 +222,4 @@ __device__ __forceinline__ void fr_upd_item_lane_call(const Ctx<RV, U, SS> &c, c
     else fr_upd_item_lane_call2<RV, U, SS, false>(c, av, T, P, fp, budget, laneId, i, algBytes);
 }
 
+}  // namespace frt

@@ -198,7 +198,7 @@ __global__ __launch_bounds__(64) void k_merge_wave(const DevModel *__restrict__ 
                                                    const uint8_t *t2, const uint8_t *ud, OutSpec o)
 {
     __shared__ Lds lds;
-    __shared__ WaveUpdLds L;
+    __shared__ WaveUpdLdsStd L;
     const DevModel &m = *mp;
     stage_model(m, lds);
     Ctx<RV, U, SS> c(m, lds);
@@ -208,7 +208,7 @@ __global__ __launch_bounds__(64) void k_merge_wave(const DevModel *__restrict__ 
         const int n1 = av.n_ent[id1], n2 = av.n_ent[id2];
         uint2 *gw = o.words + o.woff[i];
         double *ga = o.aux + o.aoff[i];
-        if (n1 > MAPLE_WU_IN || n2 > MAPLE_WU_IN) {
+        if (n1 > L.wuIn || n2 > L.wuIn) {
             if (lane == 0) {
                 Writer w;
                 w.init(gw, ga);
@@ -236,7 +236,7 @@ __global__ __launch_bounds__(64) void k_blen_wave(const DevModel *__restrict__ m
                                                   double *t, uint8_t *isFalse)
 {
     __shared__ Lds lds;
-    __shared__ WaveLds W;
+    __shared__ WaveLdsStd W;
     __shared__ double terms[128];
     const DevModel &m = *mp;
     stage_model(m, lds);
@@ -246,7 +246,7 @@ __global__ __launch_bounds__(64) void k_blen_wave(const DevModel *__restrict__ m
         const int nP = av.n_ent[idP], nC = av.n_ent[idC];
         bool f = false;
         double v = 0.0;
-        if (nP > MAPLE_WAVE_CAPW || nC > MAPLE_WAVE_CAPW) {
+        if (nP > W.capW || nC > W.capW) {
             if (threadIdx.x == 0) v = blen_walk(c, list_ref(av, idP), list_ref(av, idC), tip[i] != 0, ais + aisOff[i], 1, &f);
         } else {
             wave_sync();
@@ -261,7 +261,8 @@ __global__ __launch_bounds__(64) void k_differ_wave(const DevModel *__restrict__
                                                     uint8_t *out)
 {
     __shared__ Lds lds;
-    __shared__ unsigned long long A[MAPLE_WU_CAP], B[MAPLE_WU_CAP];
+    constexpr int cap = WaveUpdLdsStd::cap;                               // (a list that is compared: as many entries as a merged one)
+    __shared__ unsigned long long A[cap], B[cap];
     const DevModel &m = *mp;
     stage_model(m, lds);
     Ctx<RV, U, SS> c(m, lds);
@@ -271,7 +272,7 @@ __global__ __launch_bounds__(64) void k_differ_wave(const DevModel *__restrict__
         if (id2 < 0) { if (lane == 0) out[i] = 1; continue; }
         const int n1 = av.n_ent[id1], n2 = av.n_ent[id2];
         const ListRef L1 = list_ref(av, id1), L2 = list_ref(av, id2);
-        if (n1 > MAPLE_WU_CAP || n2 > MAPLE_WU_CAP) {
+        if (n1 > cap || n2 > cap) {
             if (lane == 0) out[i] = differ_walk(c, L1, L2) ? 1 : 0;
             continue;
         }
@@ -294,7 +295,7 @@ __global__ void k_wave_append(const DevModel *__restrict__ mp, ArenaView av, int
                               const uint8_t *tip, const double *bl, double *out)
 {
     __shared__ Lds lds;
-    __shared__ WaveLds wl;
+    __shared__ WaveLdsStd wl;
     const DevModel &m = *mp;
     stage_model(m, lds);
     Ctx<RV, U, SS> c(m, lds);
@@ -315,14 +316,14 @@ template <bool RV, bool U, bool SS>
 __global__ __launch_bounds__(64) void k_shorten_wave(const DevModel *__restrict__ mp, ArenaView av, int n, const int32_t *l, OutSpec o)
 {
     __shared__ Lds lds;
-    __shared__ WaveUpdLds L;
+    __shared__ WaveUpdLdsStd L;
     const DevModel &m = *mp;
     stage_model(m, lds);
     Ctx<RV, U, SS> c(m, lds);
     const int lane = threadIdx.x;
     for (int i = blockIdx.x; i < n; i += gridDim.x) {
         const int id = l[i], ne = av.n_ent[id], na = av.n_aux[id];
-        if (ne > MAPLE_WU_CAP || na > 5 * MAPLE_WU_CAP) {
+        if (ne > L.cap || na > 5 * L.cap) {
             if (lane == 0) {
                 Writer w;
                 w.init(o.words + o.woff[i], o.aux + o.aoff[i]);
@@ -464,19 +465,18 @@ template <bool RV, bool U, bool SS>
 __global__ __launch_bounds__(64) void k_evalplace_wave(MAPLE_EVALPLACE_ARGS)
 {
     __shared__ Lds lds;
-    __shared__ WaveUpdLds L;
+    __shared__ WaveUpdLdsStd L;
     const DevModel &m = *mp;
     stage_model(m, lds);
     Ctx<RV, U, SS> c(m, lds);
     const int lane = threadIdx.x;
-    WaveLds &W = *reinterpret_cast<WaveLds *>(L.baux);                     // (baux and old are not used by the merges here)
+    WaveLdsStd &W = *reinterpret_cast<WaveLdsStd *>(L.baux);               // (baux and old are not used by the merges here)
     double *terms = reinterpret_cast<double *>(L.old);
-    static_assert(sizeof(WaveLds) <= sizeof(L.baux) && 128 * sizeof(double) <= sizeof(L.old), "LDS aliases");
+    static_assert(sizeof(WaveLdsStd) <= sizeof(L.baux) && 128 * sizeof(double) <= sizeof(L.old), "LDS aliases");
     for (int i = blockIdx.x; i < n; i += gridDim.x) {
         const int idM = midTot[i], idD = down[i], idU = up[i], idR = rem[i];
         const int nMid = av.n_ent[idM], nDown = av.n_ent[idD], nUp = av.n_ent[idU], nRem = av.n_ent[idR];
-        if (nMid > MAPLE_WAVE_CAPW || nRem > MAPLE_WAVE_CAPW || nDown + nRem > MAPLE_WAVE_CAPW || nUp + nRem > MAPLE_WAVE_CAPW
-            || nUp + nDown > MAPLE_WAVE_CAPW) {
+        if (nMid > W.capW || nRem > W.capW || nDown + nRem > W.capW || nUp + nRem > W.capW || nUp + nDown > W.capW) {
             if (lane == 0)
                 evalplace_item_lane(c, av, i, midTot, down, up, dist, rem, remTip, fromTip1, sw, sa, capOff, ais, aisOff, out4, status,
                                     comp2);

@@ -100,7 +100,7 @@ __device__ __forceinline__ void spr_search_impl(const DevModel *__restrict__ mp,
     }
     Search<RV, U, SS, ASSIST> S(c, av, mv, T, P, ws);
     extern __shared__ double dynLds[];   // coop: per-depth (lastLK, failedPasses) slots of the clade scan; assisted lane searches:
-    WaveLds &wl = *(WaveLds *)dynLds;    // the staging area of the wavefront-wide appendProbNode (wave_dev.h)
+    WaveLdsStd &wl = *(WaveLdsStd *)dynLds;   // the staging area of the wavefront-wide appendProbNode (wave_dev.h)
     double *slotLK = dynLds;
     int *slotFails = (int *)(dynLds + T.scanDepthCap);
     unsigned *slotOwner = (unsigned *)(slotFails + T.scanDepthCap);
@@ -1275,7 +1275,7 @@ extern "C" int maple_spr_search_batch(maple_ctx *c, int32_t n, const int32_t *no
                 launchWaves = lanes;                                     // (the workspace is sized for `lanes` searches at a time)
             } else {
                 Tk.scan = nullptr; Tk.scanParent = nullptr; Tk.scanDepthCap = 0;
-                if (!cacheS && assistOK) dynLds = sizeof(WaveLds);
+                if (!cacheS && assistOK) dynLds = sizeof(WaveLdsStd);
             }
             // searches that update lists for hundreds of steps outgrow the per-lane list room; they carry on in chunks (one lane's
             // worth each) of a pool the launch shares instead of coming back for a second launch with 8x the room

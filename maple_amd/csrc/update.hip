@@ -72,7 +72,7 @@ template <bool RV, bool U, bool SS>
 __global__ __launch_bounds__(64) void k_update_items_wave(MAPLE_UPDATE_ITEM_ARGS)
 {
     __shared__ Lds lds;
-    __shared__ WaveUpdLds L;
+    __shared__ WaveUpdLdsStd L;
     const DevModel &m = *mp;
     stage_model(m, lds);
     Ctx<RV, U, SS> c(m, lds);
@@ -80,7 +80,7 @@ __global__ __launch_bounds__(64) void k_update_items_wave(MAPLE_UPDATE_ITEM_ARGS
     for (int i = blockIdx.x; i < n; i += gridDim.x) {
         const int id1 = l1[i], id2 = l2[i], idOld = old[i];
         const int n1 = av.n_ent[id1], n2 = av.n_ent[id2], nOld = idOld >= 0 ? av.n_ent[idOld] : 0;
-        if (n1 > MAPLE_WU_IN || n2 > MAPLE_WU_IN || nOld > MAPLE_WU_CAP) {
+        if (n1 > L.wuIn || n2 > L.wuIn || nOld > L.cap) {
             if (lane == 0) update_item_lane(c, av, n, i, l1, b1, t1, l2, b2, t2, ud, mode, old, words, aux, woff, cap, res3);
             continue;
         }

@@ -13,21 +13,20 @@
 
 namespace maple {
 
-#ifndef MAPLE_WAVE_CAPW
-#define MAPLE_WAVE_CAPW 256            // entries per list the cooperative walk stages (longer lists: one lane's walk)
-#endif
-
+template <int CAPW>
 struct WaveLds {                       // per wavefront
-    unsigned long long a[MAPLE_WAVE_CAPW], b[MAPLE_WAVE_CAPW];
-    double f[2 * MAPLE_WAVE_CAPW];
+    static constexpr int capW = CAPW;  // entries per list the cooperative walk stages (longer lists: one lane's walk)
+    unsigned long long a[CAPW], b[CAPW];
+    double f[2 * CAPW];
 };
+using WaveLdsStd = WaveLds<256>;       // the explicit-pair kernels, updatePartials and the assisted SPR search
 
-template <bool RV, bool U, bool SS>
+template <bool RV, bool U, bool SS, int CAPW>
 __device__ inline double wave_append(const Ctx<RV, U, SS> &c, ListRef P, int nP, ListRef Cl, int nC, bool isTipC, double bLen,
-                                     WaveLds &L)
+                                     WaveLds<CAPW> &L)
 {
     const int lane = threadIdx.x & 63;
-    if (nP > MAPLE_WAVE_CAPW || nC > MAPLE_WAVE_CAPW) return append_walk(c, P, Cl, isTipC, bLen);   // (every lane, same result)
+    if (nP > L.capW || nC > L.capW) return append_walk(c, P, Cl, isTipC, bLen);   // (every lane, same result)
     const unsigned long long *pw = (const unsigned long long *)P.w, *cw = (const unsigned long long *)Cl.w;
     for (int i = lane; i < nP; i += 64) L.a[i] = pw[i];
     for (int i = lane; i < nC; i += 64) L.b[i] = cw[i];

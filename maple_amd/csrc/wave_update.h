@@ -15,19 +15,18 @@
 
 namespace maple {
 
-#ifndef MAPLE_WU_IN
-#define MAPLE_WU_IN 256                // entries per input list the cooperative walks stage (longer: one lane's walk)
-#endif
-#define MAPLE_WU_CAP (2 * MAPLE_WU_IN)
-
+template <int IN>
 struct WaveUpdLds {                    // per wavefront
-    unsigned long long in[MAPLE_WU_CAP];       // words of the two input lists; later those of the shortened list
-    unsigned long long m[MAPLE_WU_CAP];        // merged list
-    unsigned long long old[MAPLE_WU_CAP];      // the list the new one is compared with
-    double maux[5 * MAPLE_WU_CAP], baux[5 * MAPLE_WU_CAP];
-    int mark[MAPLE_WU_CAP];                    // shorten: 1 = absorbed by the entry before, 2 = to be decided in order
-    unsigned long long seq[MAPLE_WU_CAP / 64];
+    static constexpr int wuIn = IN;            // entries per input list the cooperative walks stage (longer: one lane's walk)
+    static constexpr int cap = 2 * IN;         // ... of a merged list, and of a list that is shortened or compared
+    unsigned long long in[cap];                // words of the two input lists; later those of the shortened list
+    unsigned long long m[cap];                 // merged list
+    unsigned long long old[cap];               // the list the new one is compared with
+    double maux[5 * cap], baux[5 * cap];
+    int mark[cap];                             // shorten: 1 = absorbed by the entry before, 2 = to be decided in order
+    unsigned long long seq[cap / 64];
 };
+using WaveUpdLdsStd = WaveUpdLds<256>;
 
 __device__ inline void wave_sync()
 {
@@ -113,13 +112,13 @@ template <class C> __device__ __forceinline__ bool differ_step(const C &c, const
 
 // mergeVectors without the likelihood: L1, L2 -> L.m / L.maux.  Returns the number of entries (nAux: aux doubles), -1 for
 // the reference's None, -2 for a fatal state -- whatever the FIRST failing step of the walk returns.
-template <bool RV, bool U, bool SS>
+template <bool RV, bool U, bool SS, int IN>
 __device__ inline int wave_merge(const Ctx<RV, U, SS> &c, ListRef L1, int n1, double bLen1, bool tip1, ListRef L2, int n2,
-                                 double bLen2, bool tip2, bool upDown, WaveUpdLds &L, int &nAuxOut)
+                                 double bLen2, bool tip2, bool upDown, WaveUpdLds<IN> &L, int &nAuxOut)
 {
     const int lane = threadIdx.x & 63;
     const unsigned long long *w1 = (const unsigned long long *)L1.w, *w2 = (const unsigned long long *)L2.w;
-    unsigned long long *A = L.in, *B = L.in + MAPLE_WU_IN;
+    unsigned long long *A = L.in, *B = L.in + L.wuIn;
     for (int i = lane; i < n1; i += 64) A[i] = w1[i];
     for (int i = lane; i < n2; i += 64) B[i] = w2[i];
     wave_sync();
@@ -163,7 +162,7 @@ __device__ inline int wave_merge(const Ctx<RV, U, SS> &c, ListRef L1, int n1, do
 // shorten: the n entries of L.m -> the list at (gw, gaux), its words also in L.in and its aux in L.baux.  A run of R
 // entries of one kind collapses to its last entry; whether an entry with distances joins the run is decided against the
 // run's FIRST entry with a tolerance, so those (few) are decided in order.
-template <class C> __device__ inline int wave_shorten(const C &c, WaveUpdLds &L, int n, uint2 *gw, double *gaux, int &nAuxOut)
+template <class C, int IN> __device__ inline int wave_shorten(const C &c, WaveUpdLds<IN> &L, int n, uint2 *gw, double *gaux, int &nAuxOut)
 {
     const int lane = threadIdx.x & 63;
     const double thr = c.m.thresholdProb;
@@ -254,8 +253,8 @@ __device__ inline bool wave_differ(const C &c, const unsigned long long *A, cons
 // list P and the child-side list Cl (blen_step_body.inc, the text the one-lane walk runs); what the steps add to the constant
 // c1 is added in walk order (the sum is rounded term by term), the 1/(a_i+t) terms are compacted in walk order into L.f, and
 // the bracketing and bisection (blen_solve_body.inc) then run on them as they do for one lane.  `terms`: 128 doubles of LDS.
-template <bool RV, bool U, bool SS>
-__device__ inline double wave_blen(const Ctx<RV, U, SS> &c, ListRef P, int nP, ListRef Cl, int nC, bool fromTipC, WaveLds &L,
+template <bool RV, bool U, bool SS, int CAPW>
+__device__ inline double wave_blen(const Ctx<RV, U, SS> &c, ListRef P, int nP, ListRef Cl, int nC, bool fromTipC, WaveLds<CAPW> &L,
                                    double *terms, bool *isFalse)
 {
     const int lane = threadIdx.x & 63;

@@ -166,17 +166,6 @@ void k_wit_score(const DevModel *__restrict__ mp, ArenaView av, long long nPairs
     }
 }
 
-#define WIT_DISPATCH3(c, KERNEL, ...)                                                                      \
-    do {                                                                                                  \
-        const bool rv_ = (c)->dm.useRateVariation, u_ = (c)->dm.usingErrorRate, ss_ = (c)->dm.errorRateSiteSpecific; \
-        if (!rv_ && !u_) KERNEL<false, false, false> __VA_ARGS__;                                          \
-        else if (rv_ && !u_) KERNEL<true, false, false> __VA_ARGS__;                                       \
-        else if (!rv_ && u_ && !ss_) KERNEL<false, true, false> __VA_ARGS__;                               \
-        else if (!rv_ && u_ && ss_) KERNEL<false, true, true> __VA_ARGS__;                                 \
-        else if (rv_ && u_ && !ss_) KERNEL<true, true, false> __VA_ARGS__;                                 \
-        else KERNEL<true, true, true> __VA_ARGS__;                                                         \
-    } while (0)
-
 }  // namespace
 
 void witness_scratch_free(maple_ctx *c)
@@ -229,7 +218,7 @@ int witness_score(maple_ctx *c, hipStream_t st, int nQ, const int32_t *qList, co
         HIPCK(c, W.pairK.reserve_exact(std::max(W.pairK.cap, (size_t)nPairs)));
         k_wit_pairs<<<gQ, WIT_BLOCK, 0, st>>>(av, nQ, qList, W.start.p, W.bcand.p, W.qOff.p, W.pairQ.p, W.pairK.p);
         const int gP = (int)std::max<long long>(1, std::min<long long>(8192, (nPairs + WIT_BLOCK - 1) / WIT_BLOCK));
-        WIT_DISPATCH3(c, k_wit_score, <<<gP, WIT_BLOCK, 0, st>>>(c->d_model, av, nPairs, W.pairQ.p, W.pairK.p, cand, qList, qTip, qBLen, out,
+        DISPATCH3(c, k_wit_score, <<<gP, WIT_BLOCK, 0, st>>>(c->d_model, av, nPairs, W.pairQ.p, W.pairK.p, cand, qList, qTip, qBLen, out,
                                                                  ldOut, outCol, finMask, nWords));
         HIPCK(c, hipGetLastError());
     }

@@ -357,6 +357,161 @@ def test_explicit_pair_operators_one_wavefront_per_pair_are_the_one_lane_kernels
     dev.release(mark)
 
 
+def exact_list(rng, ref, u, n):
+    """A list of exactly n entries in the reference's tuple grammar (tests/list_edges.Builder): an isolated site is two entries
+    (the reference run before it and the site), a site next to the one before is one, the run to lRef the last.  The sites are
+    nucleotides, O vectors, single positions of N and single positions of the reference with a tail (what shorten() joins)."""
+    import list_edges as le
+    n_adj = int(rng.integers(20, 60)) * 2 + (n + 1) % 2                   # 2 * sites - adjacent + 1 == n
+    n_sites = (n - 1 + n_adj) // 2
+    adj = np.zeros(n_sites, dtype=bool)
+    adj[rng.choice(np.arange(1, n_sites), size=n_adj, replace=False)] = True
+    gap = np.where(adj, 0, 1)                                             # reference positions in front of each site
+    free = len(ref) - 1 - n_sites - int(gap.sum())                        # (the last position stays the closing run's)
+    iso = np.nonzero(~adj)[0]
+    gap[iso] += rng.multinomial(free, np.ones(len(iso)) / len(iso))
+    b, p = le.Builder(ref, u), 0
+    for k in range(n_sites):
+        p += int(gap[k]) + 1
+        r, kind = int(ref[p - 1]), rng.random()
+        d0 = float(rng.choice([0.0, 1e-5, 3e-4][0 if u else 1:])) if rng.random() < 0.4 else None
+        d1 = float(rng.choice([1e-5, 2e-3])) if d0 is not None and rng.random() < 0.3 else None
+        if adj[k] and kind < 0.5:
+            b.run(4, p, p, d0=float(rng.choice([1e-4, 1e-4 + 1e-10, 2e-4])), flag=bool(rng.random() < 0.8))
+        elif adj[k] and kind < 0.6:
+            b.run(5, p, p)
+        elif kind > 0.85:
+            b.o(p, le.o_vec(rng, r, float(rng.uniform(0.01, 0.6))), d0=d0)
+        else:
+            b.nuc(p, le.other(rng, r), d0=d0, d1=d1, flag=bool(rng.random() < 0.5))
+    out = b.done()
+    assert len(out) == n
+    le.check_grammar(out, len(ref), u)
+    return out
+
+
+def split_runs(gl, k):
+    """gl with its last k reference runs without a tail cut in two: k entries more, and no list operator can tell."""
+    out, pos, todo = [], [0], k
+    for e in gl:
+        pos.append(e[1] if e[0] in (4, 5) else pos[-1] + 1)
+    for i in range(len(gl) - 1, -1, -1):
+        e = gl[i]
+        out.append(e)
+        if todo and e[0] == 4 and len(e) == 2 and e[1] - pos[i] >= 2:
+            out.append((4, e[1] - 1))
+            todo -= 1
+    assert todo == 0
+    return out[::-1]
+
+
+def change_nucs(rng, gl, k):
+    """gl with another nucleotide at its last site and at k - 1 more of its sites that hold one."""
+    import list_edges as le
+    at = [i for i, e in enumerate(gl) if e[0] < 4]
+    out = list(gl)
+    for i in [at[-1]] + [int(x) for x in rng.choice(at[:-1], size=k - 1, replace=False)]:
+        out[i] = (le.other(rng, gl[i][1], (gl[i][0],)),) + gl[i][1:]
+    return out
+
+
+@pytest.mark.parametrize("mode", ["unrest", "siteerr"])
+def test_explicit_pair_wavefront_kernels_at_their_staging_limits(mode):
+    """The explicit-pair wavefront kernels on lists of exactly one entry less than, as many as and one entry more than they stage:
+    255 / 256 / 257 entries per list for k_merge_wave, k_wave_append and k_blen_wave (WaveUpdLdsStd::wuIn, WaveLdsStd::capW: the
+    sizes of k_update_items_wave's inputs too), 511 / 512 / 513 for k_differ_wave and k_shorten_wave (WaveUpdLdsStd::cap).  All nine
+    ordered size pairs, by wavefronts and by lanes (wave_per_item_max = -1): words and doubles bit for bit; the wavefront form
+    against the oracle at the bars of test_hip_list_edges.py (appendProbNode 1e-12, the others 1e-9, structure exact); and the
+    debug library's wavefront append on the same pairs.
+    (What this can and cannot see: the oracle knows nothing of the kernels' routes, and a list beyond the limit is walked by
+    lane 0 with the same result.  A limit that is off by one towards the one-lane walk therefore still passes; one that is off
+    towards the staged walk overruns the staging and does not.)"""
+    import list_edges as le
+    from golden_util import close, lists_match
+    from maple_amd.runtime import Device
+    from oracle.oracle_py import Oracle
+    ref, kw = le.reference(), le.model(mode)
+    u = bool(kw.get("usingErrorRate"))
+    dev = Device(ref, le.ROOT_FREQS, arena_bytes=256 << 20)
+    dbg = Device(ref, le.ROOT_FREQS, arena_bytes=256 << 20, debug=True)
+    orc = Oracle(ref, le.ROOT_FREQS)
+    for x in (dev, dbg, orc):
+        x.set_model(**kw)
+    rng = np.random.default_rng(61 + len(mode))
+    # sets 0, 1: unrelated lists; sets 2, 3: the first list of set 0 and a list six nucleotides away from it (a branch length
+    # to estimate, few factors to multiply), each cut to the three sizes
+    small = [[exact_list(rng, ref, u, n) for n in (255, 256, 257)] for _ in range(2)]
+    small += [[split_runs(g, k) for k in (0, 1, 2)] for g in (small[0][0], change_nucs(rng, small[0][0], 6))]
+    base = exact_list(rng, ref, u, 511)
+    big = [[split_runs(g, k) for k in (0, 1, 2)] for g in (base, change_nucs(rng, base, 1))]
+    ids_s, ids_b = [dev.upload(x) for x in small], [dev.upload(x) for x in big]
+    for ids, want in ((ids_s, [255, 256, 257]), (ids_b, [511, 512, 513])):
+        for row in ids:
+            assert dev.sizes(row)[0].tolist() == want
+    ij = [(i, j) for i in range(3) for j in range(3)]
+    # the 256 class: (list of set a, list of set a ^ 1), the child's as a tip's and as an internal node's
+    pairs = [(a, i, a ^ 1, j, t) for a in range(4) for i, j in ij for t in (False, True)]
+    P = np.asarray([ids_s[a][i] for a, i, b, j, t in pairs])
+    Cl = np.asarray([ids_s[b][j] for a, i, b, j, t in pairs])
+    lP, lC = [small[a][i] for a, i, b, j, t in pairs], [small[b][j] for a, i, b, j, t in pairs]
+    tip = np.asarray([t for *_, t in pairs])
+    bl = np.asarray([[1e-5, 1e-3, 0.0][k % 3] for k in range(len(pairs))])
+    b2 = np.asarray([[2e-4, 1e-5][k % 2] for k in range(len(pairs))])
+    ud = np.asarray([k % 4 == 1 for k in range(len(pairs))])
+    # the 512 class: the same list cut differently (not different), and against the list with another last nucleotide
+    dpairs = [(0, i, b, j) for b in (0, 1) for i, j in ij] + [(1, i, 0, j) for i, j in ij]
+    D1, D2 = np.asarray([ids_b[a][i] for a, i, b, j in dpairs]), np.asarray([ids_b[b][j] for a, i, b, j in dpairs])
+    S = np.concatenate(ids_b)
+    assert len(pairs) * 3 + len(dpairs) + len(S) < 1024
+
+    def run():
+        mg = dev.merge_batch(P, bl + 1e-5, False, Cl, b2, tip, ud)
+        sh = dev.shorten_batch(S)
+        return dict(app=dev.append_batch(P, Cl, tip, bl), blen=dev.blen_batch(P, Cl, tip), dif=dev.differ_batch(D1, D2), mg=mg, sh=sh,
+                    mg_pk=dev.download_packed(mg[mg >= 0]), sh_pk=dev.download_packed(sh))
+
+    wave = run()
+    dev.set_tuning(wave_per_item_max=-1)
+    lane = run()
+    dev.set_tuning()
+    dwave, _ = dbg.debug_wave_append_batch(dbg.upload(lP), dbg.upload(lC), tip, bl)
+    got_mg = dev.download(wave["mg"])
+    got_sh = dev.download(wave["sh"])
+    dev.close()
+    dbg.close()
+    # wavefronts against lanes: bit for bit
+    assert np.array_equal(wave["app"].view(np.uint64), lane["app"].view(np.uint64))
+    assert np.array_equal(wave["app"].view(np.uint64), dwave.view(np.uint64))
+    assert np.array_equal(wave["blen"][0].view(np.uint64), lane["blen"][0].view(np.uint64)) and np.array_equal(wave["blen"][1], lane["blen"][1])
+    assert np.array_equal(wave["dif"], lane["dif"])
+    assert np.array_equal(wave["mg"] >= 0, lane["mg"] >= 0) and (wave["mg"] >= 0).sum() > len(pairs) // 2
+    for k in ("mg_pk", "sh_pk"):
+        for a in ("ent_off", "pos", "meta", "aux_off"):
+            assert np.array_equal(getattr(wave[k], a), getattr(lane[k], a)), (k, a)
+        assert np.array_equal(wave[k].aux.view(np.uint64), lane[k].aux.view(np.uint64)), k
+    # wavefronts against the oracle
+    for k, (a, i, b, j, t) in enumerate(pairs):
+        want = orc.appendProbNode(lP[k], lC[k], bool(t), float(bl[k]))
+        g = float(wave["app"][k])
+        assert (g == want) if (math.isinf(want) or math.isinf(g)) else close(g, want, 1e-12), ("append", k, g, want)
+        want = orc.estimateBranchLengthWithDerivative(lP[k], lC[k], bool(t))
+        if want is False:
+            assert wave["blen"][1][k], ("blen", k)
+        else:
+            assert not wave["blen"][1][k] and close(float(wave["blen"][0][k]), want, 1e-9), ("blen", k, wave["blen"][0][k], want)
+        want = orc.mergeVectors(lP[k], float(bl[k]) + 1e-5, False, lC[k], float(b2[k]), bool(t), isUpDown=bool(ud[k]))
+        assert lists_match(got_mg[k], want, 1e-9), ("merge", k)
+    big_flat = [g for row in big for g in row]
+    for k, (a, i, b, j) in enumerate(dpairs):
+        assert bool(wave["dif"][k]) == bool(orc.areVectorsDifferent(big[a][i], big[b][j])) == (a != b), ("differ", k)
+    n_shorter = 0
+    for k, g in enumerate(big_flat):
+        want = orc.shorten(g)
+        assert lists_match(got_sh[k], want, 1e-9), ("shorten", k)
+        n_shorter += len(want) < len(g)
+    assert n_shorter >= 4                                                 # (at least the runs cut in two are joined again)
+
+
 def test_wavefront_wide_update_items_leave_the_one_lane_lists(world, monkeypatch):
     """k_update_items_wave (one wavefront per item: mergeVectors, shorten and areVectorsDifferent cut along the merge path,
     wave_update.h) against k_update_items (one lane per item), in every model mode: the same 60 changes -- one at a time,
@@ -890,6 +1045,58 @@ def test_frontier_levels_by_wavefronts_or_by_lanes_give_the_same_searches(mode):
             for k in ("status", "bestNode", "placement", "nAppend", "bestScore", "currentLK", "improvement", "blen"):
                 assert np.array_equal(r[k], res[0][k]), (form, k)
         assert (res[0]["status"] == 0).sum() > 4000
+    dev.close()
+
+
+@pytest.mark.parametrize("mode", ["ratevar", "siteerr"])
+def test_frontier_wavefront_size_classes_are_both_used_and_equal_the_lane_forms(mode):
+    """The wavefront-wide items of a frontier level come in two size classes (frt::WaveSmall / frt::WaveBig, frontier_dev.h:
+    k_fr_sort_level lists an item for the class whose staging its lists fit, k_fr_updating_wave_s / k_fr_updating_wave take
+    them).  A 400-tip tree of divergent samples (60 differences on average: tip lists of 17 to 257 entries, most of them at
+    most 128) with every level by wavefronts: BOTH classes get items, and the searches are those of a lane per item and of the
+    one-lane-per-search kernels, bit for bit, on the plain tree and with MAT local references."""
+    import bench
+    from maple_amd.host import reference_tables, tip_genome_list
+    from maple_amd.mat import add_local_references
+    from maple_amd.runtime import Device
+    from maple_amd.synth import make_dataset
+    from maple_amd.tree_host import HostTree
+    from maple_amd.tree_mirror import TreeMirror
+    data = make_dataset(n_samples=400, l_ref=29903, seed=9, mean_diffs=60.0, frac_with_n=0.1, frac_ambig=0.05)
+    ref_idx, rf = reference_tables(data.ref)
+    mkw = world_model_kwargs(mode, len(ref_idx), 9)
+    dev = Device(ref_idx, rf, arena_bytes=1 << 30, debug=True)
+    dev.set_model(**mkw)
+    tip_kw = dict(error_rates=mkw["errorRates"]) if mode == "siteerr" else {}
+    tips = {int(v): tip_genome_list(dl, ref_idx, **tip_kw) for v, dl in zip(data.tip_node, data.diffs)}
+    m = TreeMirror(dev, data.parent, data.blen, tips).build()
+    kw = bench.search_kwargs(dev.lRef)
+    nodes = bench.preorder_nodes(m)
+    ht = HostTree.from_mirror(m)
+    for form in ("plain", "local references"):
+        if form == "plain":
+            dev.upload_tree(m.root, m.parent, m.children[:, 0], m.children[:, 1], m.dist, m.is_tip, m.lower, m.up_right, m.up_left, m.tot_up,
+                            -np.ones(m.n_nodes, dtype=np.int32))
+        else:
+            assert add_local_references(dev, ht, 40) > 0
+            dist = np.asarray([float(x or 0.0) for x in ht.dist])
+            dev.upload_tree(ht.root, m.parent, m.children[:, 0], m.children[:, 1], dist, m.is_tip, ht.id_lower, ht.id_upRight, ht.id_upLeft,
+                            ht.id_totUp, ht.id_mut)
+        res = []
+        for wab in (-1, 1 << 30):
+            dev.set_tuning(wave_all_below=wab)
+            res.append(dev.spr_search_batch(nodes, wide_search_budget=-1, **kw))
+        if form == "plain":
+            dev.frontier_levels()
+            n_small, n_big = (int(x.sum()) for x in dev.last_wave_items)
+            print(f"wavefront-wide items, {mode}: {n_small} small class, {n_big} big class")
+            assert n_small > 0 and n_big > 0, (n_small, n_big)
+        dev.set_tuning()
+        res.append(dev.spr_search_batch(nodes, search_tier=1, wide_search_budget=-1, **kw))
+        for r in res[1:]:
+            for k in ("status", "bestNode", "placement", "nAppend", "bestScore", "currentLK", "improvement", "blen"):
+                assert np.array_equal(r[k], res[0][k]), (form, k)
+        assert (res[0]["status"] == 0).any()
     dev.close()
 
 
