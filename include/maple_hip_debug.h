@@ -44,6 +44,15 @@ int maple_debug_gpv_batch(maple_ctx *ctx, int32_t n, const int32_t *i12, const d
                           const double *errorRate, const double *vect4, const uint8_t *upNode, const uint8_t *flag,
                           double *out4);
 int maple_debug_simplify_batch(maple_ctx *ctx, int32_t n, const double *vec4, const int32_t *refA, int32_t *out);
+/* passGenomeListThroughBranch of a REMOVED list as the frontier tier of the SPR search runs it (maple_amd/csrc/frontier_dev.h),
+ * for n (list, mutation list or -1, direction) items: waveForm 0 = one lane per item (fpass_removed: fpass_store, then
+ * shorten_would_merge), 1 = one wavefront per item (wave_pass with `removed` set).  outList[i] = a new list with the result, or
+ * list[i] itself where the tier hands the input handle back (no mutations on the branch: sameHandle[i] = 1); grade[i] = what the
+ * tier marks the new list with -- 0: shorten() (M:7087) would leave it as it is, 1: it would merge entries whose tails are the
+ * same doubles and flag, 2: it would merge tails that are equal only within thresholdProb.  The hook compiles the tier's device
+ * functions into kernels of its own: it checks the source the search is built from, not the search's object code. */
+int maple_debug_frontier_pass_batch(maple_ctx *ctx, int32_t n, const int32_t *list, const int32_t *mutList, const uint8_t *dirIsUp,
+                                    int32_t waveForm, int32_t *outList, uint8_t *grade, uint8_t *sameHandle);
 
 #ifdef __cplusplus
 }

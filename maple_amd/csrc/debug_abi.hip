@@ -5,8 +5,11 @@
 #include "ctx_host.h"
 #include "batch_host.h"
 #include "frontier.h"
+#include "frontier_dev.h"
 
 #include <algorithm>
+
+using namespace frt;
 
 // Calibration of the FETCH_SIZE counter for THIS library's access pattern (MI355X_MICROARCH.md, HBM section: the
 // counter is only calibrated for 16 B/lane coalesced streams).  Every lane walks its own contiguous 512-byte "list"
@@ -209,5 +212,127 @@ extern "C" int maple_debug_frontier_levels(maple_ctx *c, int32_t cap, int64_t *i
     const int rc = frontier_level_profile(c, cap, (long long *)itemsUpdating, (long long *)itemsCached, msUpdating, msCached, &nn,
                                           (long long *)waveItemsSmall, (long long *)waveItemsBig);
     *n = nn;
+    return rc;
+}
+
+// ---- passGenomeListThroughBranch of a removed list as the frontier tier of the SPR search runs it (frontier_dev.h) ---------------
+// The tier's two forms -- one lane per item (fpass_removed: fpass_store + shorten_would_merge) and one wavefront per item
+// (wave_pass with `removed` set) -- are reached in the product only from inside a search on a tree with MAT local references.
+// These two kernels call them as k_fr_pass / k_fr_pass_wave (frontier.hip) do, on n items of the caller, over the least of an
+// FPools they read: the temporary lists' pool with its records, flags and counters, a scratch slab per lane, the mutation view.
+template <bool RV, bool U, bool SS>
+__global__ __launch_bounds__(FR_BLOCK) void k_debug_fpass_lane(const DevModel *__restrict__ mp, ArenaViewS av, FPools fp, int n, const int32_t *l,
+                                                               const int32_t *ml, const uint8_t *up, int32_t *handle)
+{
+    __shared__ Lds lds;
+    const DevModel &m = *mp;
+    stage_model(m, lds);
+    Ctx<RV, U, SS> c(m, lds);
+    const long long laneId = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    for (long long i = laneId; i < n; i += (long long)gridDim.x * blockDim.x)
+        handle[i] = fpass_removed(c, fp, av, laneId, ftree(l[i]), ml[i], up[i] != 0);
+}
+
+template <bool RV, bool U, bool SS>
+__global__ __launch_bounds__(FR_BLOCK) void k_debug_fpass_wave(const DevModel *__restrict__ mp, ArenaViewS av, FPools fp, int n, const int32_t *l,
+                                                               const int32_t *ml, const uint8_t *up, int32_t *handle)
+{
+    __shared__ Lds lds;
+    const DevModel &m = *mp;
+    stage_model(m, lds);
+    Ctx<RV, U, SS> c(m, lds);
+    const long long wave = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6, nWaves = ((long long)gridDim.x * blockDim.x) >> 6;
+    const int lane = threadIdx.x & 63;
+    for (long long i = wave; i < n; i += nWaves) {
+        const int h = wave_pass(c, fp, av, ftree(l[i]), ml[i], up[i] != 0, true);
+        if (lane == 0) handle[i] = h;
+    }
+}
+
+// where each item's new temporary list lies, for commit_lists (n_ent -1: the item got its own handle back, or none), and its grade
+__global__ __launch_bounds__(FR_BLOCK) void k_debug_fpass_out(FPools fp, int n, const int32_t *handle, int64_t *woff, int64_t *aoff, int32_t *nEnt,
+                                                              int32_t *nAux, uint8_t *grade)
+{
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        const int h = handle[i];
+        if (h >= 0 && h < fp.capL) {
+            const LRec r = fp.trec[h];
+            woff[i] = LREC_OFF(r.x); aoff[i] = LREC_OFF(r.y); nEnt[i] = LREC_N(r.x); nAux[i] = LREC_N(r.y); grade[i] = fp.tflag[h];
+        } else { woff[i] = 0; aoff[i] = 0; nEnt[i] = -1; nAux[i] = 0; grade[i] = 0; }
+    }
+}
+
+extern "C" int maple_debug_frontier_pass_batch(maple_ctx *c, int32_t n, const int32_t *list, const int32_t *mutList, const uint8_t *dirIsUp,
+                                               int32_t waveForm, int32_t *outList, uint8_t *grade, uint8_t *sameHandle)
+{
+    if (!c || n < 0 || n > (1 << 20) || !list || !mutList || !dirIsUp || !outList || !grade || !sameHandle) return MAPLE_ERR_ARG;
+    if (n == 0) return MAPLE_OK;
+    HIPCK(c, hipSetDevice(c->device));
+    TRY(need_model(c));
+    TRY(check_ids(c, n, list, false, "list"));
+    TRY(settle(c));
+    const int32_t nml = (int32_t)c->h_mut_cnt.size();
+    // the most a pass writes: two entries per mutation, each with the tail of the run it splits (<= 2 doubles)
+    long long capW = 0, capA = 0;
+    int capE = 1;
+    for (int i = 0; i < n; i++) {
+        if (mutList[i] < -1 || mutList[i] >= nml) return fail(c, MAPLE_ERR_ARG, "mutList[%d] = %d is not a mutation-list id", i, mutList[i]);
+        const long long cnt = mutList[i] < 0 ? 0 : c->h_mut_cnt[mutList[i]];
+        const long long ne = c->h_n_ent[list[i]] + 2 * cnt, na = c->h_n_aux[list[i]] + 4 * cnt;
+        capW += ne; capA += na;
+        capE = std::max(capE, (int)ne);
+    }
+    const int threads = waveForm ? 64 * std::min(n, 1024) : std::min(1024, (n + FR_BLOCK - 1) / FR_BLOCK * FR_BLOCK);
+    const int grid = (threads + FR_BLOCK - 1) / FR_BLOCK;
+    const long long lanes = (long long)grid * FR_BLOCK;
+    HIPCK(c, c->s_words.reserve((size_t)capW));
+    HIPCK(c, c->s_aux.reserve((size_t)capA));
+    // one allocation for the rest: list records, flags, counters, the lanes' scratch slabs, the items' results
+    auto up16 = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const size_t oRec = 0, oCtr = up16(oRec + (size_t)n * sizeof(LRec)), oSw = up16(oCtr + sizeof(FCtr)),
+                 oSa = up16(oSw + (waveForm ? 0 : (size_t)lanes * capE * sizeof(uint2))),
+                 oWoff = up16(oSa + (waveForm ? 0 : (size_t)lanes * 5 * capE * sizeof(double))), oAoff = up16(oWoff + (size_t)n * 8),
+                 oHandle = up16(oAoff + (size_t)n * 8), oNe = up16(oHandle + (size_t)n * 4), oNa = up16(oNe + (size_t)n * 4),
+                 oFlag = up16(oNa + (size_t)n * 4), oGrade = up16(oFlag + (size_t)n), total = up16(oGrade + (size_t)n);
+    uint8_t *buf = nullptr;
+    HIPCK(c, hipMalloc((void **)&buf, total));
+    int rc = MAPLE_OK;
+    std::vector<int32_t> handle(n);
+    do {
+        if (hipMemsetAsync(buf, 0, oSw, c->stream) != hipSuccess) { rc = fail(c, MAPLE_ERR_HIP, "hipMemsetAsync"); break; }
+        FPools fp;
+        memset(&fp, 0, sizeof fp);
+        fp.tw = c->s_words.p; fp.ta = c->s_aux.p;
+        fp.trec = (LRec *)(buf + oRec); fp.tflag = buf + oFlag;
+        fp.capW = capW; fp.capA = capA; fp.capL = n;
+        fp.sw = (uint2 *)(buf + oSw); fp.sa = (double *)(buf + oSa); fp.capE = capE;
+        fp.ctr = (FCtr *)(buf + oCtr);
+        fp.mat = 1;
+        fp.mv = MutViewS{c->d_mut3, c->d_mut_off, c->d_mut_cnt};
+        const ArenaViewS av{c->d_words, c->d_aux, c->d_ent_off, c->d_aux_off, c->d_n_ent, c->d_n_aux};
+        if ((rc = stage_begin(c, (size_t)n * 64 + 256)) != MAPLE_OK) break;
+        auto *dl = stage_put(c, list, (size_t)n);
+        auto *dml = stage_put(c, mutList, (size_t)n);
+        auto *dup = stage_put(c, dirIsUp, (size_t)n);
+        if (!dl || !dml || !dup) { rc = fail(c, MAPLE_ERR_NOMEM, "argument staging overflow"); break; }
+        if ((rc = stage_flush(c)) != MAPLE_OK) break;
+        int32_t *dHandle = (int32_t *)(buf + oHandle), *dNe = (int32_t *)(buf + oNe), *dNa = (int32_t *)(buf + oNa);
+        int64_t *dWoff = (int64_t *)(buf + oWoff), *dAoff = (int64_t *)(buf + oAoff);
+        if (waveForm) DISPATCH3(c, k_debug_fpass_wave, <<<grid, FR_BLOCK, 0, c->stream>>>(c->d_model, av, fp, n, dl, dml, dup, dHandle));
+        else DISPATCH3(c, k_debug_fpass_lane, <<<grid, FR_BLOCK, 0, c->stream>>>(c->d_model, av, fp, n, dl, dml, dup, dHandle));
+        hipLaunchKernelGGL(k_debug_fpass_out, dim3(grid_for(n)), dim3(FR_BLOCK), 0, c->stream, fp, n, dHandle, dWoff, dAoff, dNe, dNa, buf + oGrade);
+        if (hipGetLastError() != hipSuccess || hipMemcpyAsync(handle.data(), dHandle, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess
+            || hipMemcpyAsync(grade, buf + oGrade, (size_t)n, hipMemcpyDeviceToHost, c->stream) != hipSuccess
+            || hipStreamSynchronize(c->stream) != hipSuccess) { rc = fail(c, MAPLE_ERR_HIP, "the frontier pass hook's launch failed"); break; }
+        for (int i = 0; i < n && rc == MAPLE_OK; i++) {
+            sameHandle[i] = handle[i] == -(list[i] + 10);
+            if (!sameHandle[i] && handle[i] < 0) rc = fail(c, MAPLE_ERR_NOMEM, "item %d: no room for the new list (%d)", i, handle[i]);
+        }
+        if (rc != MAPLE_OK) break;
+        if ((rc = commit_lists(c, n, dWoff, dAoff, dNe, dNa, outList, fp.tw, fp.ta)) != MAPLE_OK) break;
+        if (hipStreamSynchronize(c->stream) != hipSuccess) { rc = fail(c, MAPLE_ERR_HIP, "hipStreamSynchronize"); break; }
+        for (int i = 0; i < n; i++) if (sameHandle[i]) outList[i] = list[i];
+    } while (0);
+    (void)hipFree(buf);
     return rc;
 }

@@ -31,7 +31,8 @@ EXPORTS = [
 
 # include/maple_hip_debug.h: measurement aids and test hooks, exported by libmaple_hip_debug.so only (Device(..., debug=True))
 DEBUG_EXPORTS = ["maple_debug_wave_append_batch", "maple_debug_trace_query", "maple_debug_trace_read", "maple_debug_calib_walk",
-                 "maple_debug_calib_write", "maple_debug_gpv_batch", "maple_debug_simplify_batch", "maple_debug_frontier_levels"]
+                 "maple_debug_calib_write", "maple_debug_gpv_batch", "maple_debug_simplify_batch", "maple_debug_frontier_levels",
+                 "maple_debug_frontier_pass_batch"]
 LIB_PATH_DEBUG = os.path.join(HERE, "libmaple_hip_debug.so")
 
 
@@ -559,6 +560,19 @@ class Device:
         out = np.zeros(len(v), dtype=np.int32)
         self._ck(self.lib.maple_debug_simplify_batch(self.h, len(v), _ptr(v), _ptr(_i32(refA)), _ptr(out)))
         return out
+
+    def debug_frontier_pass_batch(self, lists, mutLists, dirIsUp, wave_form=False):
+        """passGenomeListThroughBranch of removed lists as the frontier tier of the SPR search runs it
+        (maple_debug_frontier_pass_batch): one lane per item, or one wavefront per item with wave_form.  Returns (list ids --
+        the input id where the tier handed its handle back --, grades 0 / 1 / 2, same-handle flags)."""
+        lists, mutLists = _i32(lists), _i32(mutLists)
+        n = len(lists)
+        up = _u8(np.broadcast_to(dirIsUp, n))
+        out = np.zeros(n, dtype=np.int32)
+        grade, same = np.zeros(n, dtype=np.uint8), np.zeros(n, dtype=np.uint8)
+        self._ck(self.lib.maple_debug_frontier_pass_batch(self.h, n, _ptr(lists), _ptr(mutLists), _ptr(up), int(bool(wave_form)),
+                                                          _ptr(out), _ptr(grade), _ptr(same)))
+        return out, grade, same.astype(bool)
 
     def debug_calib_walk(self, nbytes, repeats=1):
         ms = C.c_float()

@@ -475,6 +475,19 @@ int maple_root_prob_batch(maple_ctx *c, int32_t n, const int32_t *l, double *out
     return MAPLE_OK;
 }
 
+int maple_minor_batch(maple_ctx *c, int32_t n, const int32_t *l1, const int32_t *l2, int onlyFindIdentical, uint8_t *out)
+{
+    if (!c || n < 0 || !l1 || !l2 || !out) return MAPLE_ERR_ARG;
+    NEED_MODEL(c);
+    for (int i = 0; i < n; i++) {
+        NEED_ID(c, l1[i], "list1"); NEED_ID(c, l2[i], "list2");
+        const int r = omo_isMinorSequence(&c->m, LIST(c, l1[i]), c->len[l1[i]], LIST(c, l2[i]), c->len[l2[i]], onlyFindIdentical != 0);
+        if (r < 0) return fail(c, MAPLE_ERR_FATAL, "isMinorSequence: item %d", i);
+        out[i] = (uint8_t)r;
+    }
+    return MAPLE_OK;
+}
+
 int maple_evaluate_placement_batch(maple_ctx *c, int32_t n, const int32_t *mid, const int32_t *down, const int32_t *up, const double *distance,
                                    const int32_t *rem, const uint8_t *isRemovedTip, const uint8_t *fromTip1, double *out4)
 {

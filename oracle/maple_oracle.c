@@ -16,29 +16,13 @@
 #define U_(m) ((m)->usingErrorRate)
 
 /* Branch counters for the coverage gate of tests/test_list_edges_coverage.py: compiled in only with -DOMO_BRANCH_COUNTS (the
- * default build, the one the golden tests pin, has none).  Each counts one rarely taken branch of the operators below. */
+ * default build, the one the golden tests pin, has none).  Each counts one rarely taken branch of the operators below and of
+ * maple_oracle_search.c; maple_oracle_bc.h lists them. */
 #ifdef OMO_BRANCH_COUNTS
-enum {
-    BC_APPEND_R_D1_O,           /* appendProbNode: R with d0 and d1 against an O vector at <= 0.02, M:6611-6633 */
-    BC_APPEND_NUC_D1_O,         /* appendProbNode: nucleotide with d0 and d1 against an O vector at <= 0.02, M:6744-6761 */
-    BC_APPEND_CARRY3,           /* appendProbNode: a third carry-over within one call, M:6772-6783 */
-    BC_MERGE_CARRY,             /* mergeVectors(returnLK): the running factor carried over into the log, M:4830-4839 */
-    BC_MERGE_UNDERFLOW,         /* mergeVectors(returnLK): the running factor below DBL_MIN (the reference raises, M:4831-4836) */
-    BC_MERGE_UPDOWN_N_ERR_D0,   /* mergeVectors(isUpDown), error model: N against an entry that carries d0, M:4517-4518 */
-    BC_MERGE_UPDOWN_N_O_ZERO,   /* mergeVectors(isUpDown): N against an O vector of total length 0, M:4560-4561 */
-    BC_BLEN_NONE_R_D1,          /* estimateBranchLengthWithDerivative: None, R with d1 against a zero rate, M:5171-5172 */
-    BC_BLEN_NONE_R_FLAG,        /* ... None, tail-less R against a flagged nucleotide over a zero rate, M:5178-5179 */
-    BC_BLEN_NONE_NUC_D1,        /* ... None, nucleotide with d1 against a zero rate, M:5241-5242 */
-    BC_BLEN_EARLY_TENTH,        /* ... the early return of 0.1 when vDown > c1 + sens and tDown >= 0.1, M:5341-5342 */
-    BC_EVALPLACE_TOP_FALLBACK,  /* evaluatePlacement: the top merge returned None, bestTop = defaultBLen * 0.1, M:6798-6802 */
-    BC_N
-};
-static const char *const omo_bc_names[BC_N] = {
-    "append_R_d1_O", "append_nuc_d1_O", "append_carry3", "merge_carry", "merge_underflow", "merge_updown_N_err_d0",
-    "merge_updown_N_O_zero", "blen_none_R_d1", "blen_none_R_flag", "blen_none_nuc_d1", "blen_early_tenth",
-    "evalplace_top_fallback"};
-static long long omo_bc[BC_N];
-#define BC(k) __atomic_fetch_add(&omo_bc[k], 1, __ATOMIC_RELAXED)
+#include "maple_oracle_bc.h"
+#define OMO_BC_NAME_(e, n) n,
+static const char *const omo_bc_names[BC_N] = {OMO_BC_LIST(OMO_BC_NAME_)};
+long long omo_bc[BC_N];
 /* copies up to n counters into out (and their names into names, if given), zeroes them when reset; returns how many exist */
 int omo_branch_counts(long long *out, const char **names, int n, int reset)
 {
@@ -137,6 +121,19 @@ int omo_simplify(const OModel *m, const double *vec, int refA, int *state)
     return 0;
 }
 
+#ifdef OMO_BRANCH_COUNTS
+/* shorten's test of one pair, for the counters alone: 1 absorb, 0 refused on a length, -1 refused on the flag alone */
+static int bc_shorten_pair(const OModel *m, const OEntry *nw, const OEntry *old)
+{
+    if (nw->len == 2) return 1;
+    if (fabs(nw->d0 - old->d0) > m->thresholdProb) return 0;
+    if (nw->len == 3) return 1;
+    if (U_(m) && nw->len == 4) return nw->flag == old->flag ? 1 : -1;
+    if (fabs(nw->d1 - old->d1) > m->thresholdProb) return 0;
+    return (nw->len == 4 || nw->flag == old->flag) ? 1 : -1;
+}
+#endif
+
 /* ---- shorten, M:3721-3745 (in place; returns the new length) --------------- */
 int omo_shorten(const OModel *m, OEntry *vec, int n)
 {
@@ -160,6 +157,15 @@ int omo_shorten(const OModel *m, OEntry *vec, int n)
                 else if (nw.len == 4 || nw.flag == old.flag) pop = 1;
                 else pop = 0;
             }
+#ifdef OMO_BRANCH_COUNTS
+            {
+                const int head = bc_shorten_pair(m, &nw, &old), nb = bc_shorten_pair(m, &nw, &vec[index]);
+                if (pop) BC(BC_SHORTEN_ABSORB_LEN2 + nw.len - 2);
+                if (head == -1) BC(BC_SHORTEN_REFUSE_FLAG);
+                if (head == 0 && nb != 0) BC(BC_SHORTEN_REFUSE_HEAD_FAR);
+                if (head != 0 && nb == 0) BC(BC_SHORTEN_HEAD_NEAR_NEIGHBOUR_FAR);
+            }
+#endif
         }
         if (pop) {
             memmove(&vec[index], &vec[index + 1], (size_t)(n - index - 1) * sizeof(OEntry));
@@ -181,10 +187,22 @@ int omo_passGenomeListThroughBranch(const OModel *m, const OEntry *pv, int n, co
     int iM = 0, iE = 0, lastPos = 0, no = 0;
     const OEntry *e = &pv[iE];
     (void)n;
+#ifdef OMO_BRANCH_COUNTS
+    if (lMut > 0 && mut[0] == 1) BC(BC_PASS_MUT_AT_1_DOWN + !!dirIsUp);
+    if (lMut > 0 && mut[(lMut - 1) * 3] == lRef) BC(BC_PASS_MUT_AT_LREF_DOWN + !!dirIsUp);
+#endif
     for (;;) {
         if (e->type == 5) {                                          /* M:3758-3768 */
             out[no++] = *e;
             lastPos = e->x;
+#ifdef OMO_BRANCH_COUNTS
+            {   /* (counted before the early exit: an N run that ends the list skips its mutations all the same) */
+                int k = iM;
+                while (k < lMut && mut[k * 3] <= lastPos) k++;
+                if (k - iM == 1) BC(BC_PASS_N_SKIP_ONE_DOWN + !!dirIsUp);
+                if (k - iM > 1) BC(BC_PASS_N_SKIP_MANY_DOWN + !!dirIsUp);
+            }
+#endif
             if (lastPos == lRef) break;
             while (iM < lMut && mut[iM * 3] <= lastPos) iM++;
             e = &pv[++iE];
@@ -194,20 +212,28 @@ int omo_passGenomeListThroughBranch(const OModel *m, const OEntry *pv, int n, co
                 int from = mut[iM * 3 + 1], to = mut[iM * 3 + 2];
                 int cmp = dirIsUp ? from : to;
                 OEntry ne = *e;
-                if (e->type == cmp) { ne.type = 4; ne.x = lastPos; }
-                else { ne.type = e->type; ne.x = cmp; }
+                if (e->type == cmp) { ne.type = 4; ne.x = lastPos; BC((e->len > 2 ? BC_PASS_NUC_TO_R_TAIL_DOWN : BC_PASS_NUC_TO_R_DOWN) + !!dirIsUp); }
+                else { ne.type = e->type; ne.x = cmp; BC(BC_PASS_NUC_KEEPS_DOWN + !!dirIsUp); }
                 iM++;
                 out[no++] = ne;
             } else out[no++] = *e;
             if (lastPos == lRef) break;
             e = &pv[++iE];
         } else if (e->type == 4) {                                   /* M:3808-3852 */
+#ifdef OMO_BRANCH_COUNTS
+            int nInRun = 0;
+#endif
             while (iM < lMut && mut[iM * 3] <= e->x) {
                 if (mut[iM * 3] > lastPos + 1) {
                     lastPos = mut[iM * 3] - 1;
                     OEntry ne = *e; ne.x = lastPos;
                     out[no++] = ne;
                 }
+#ifdef OMO_BRANCH_COUNTS
+                else BC((nInRun ? BC_PASS_R_MUT_ADJACENT_DOWN : BC_PASS_R_MUT_FIRST_DOWN) + !!dirIsUp);
+                if (++nInRun == 3) BC(BC_PASS_R_MUT_THREE_DOWN + !!dirIsUp);
+                if (nInRun == 1 && e->len > 2) BC(BC_PASS_R_TAIL_LEN3_DOWN + 2 * (e->len - 3) + !!dirIsUp);
+#endif
                 lastPos += 1;
                 OEntry ne = *e;
                 if (dirIsUp) { ne.type = mut[iM * 3 + 2]; ne.x = mut[iM * 3 + 1]; }
@@ -216,6 +242,9 @@ int omo_passGenomeListThroughBranch(const OModel *m, const OEntry *pv, int n, co
                 out[no++] = ne;
             }
             if (lastPos < e->x) { lastPos = e->x; out[no++] = *e; }
+#ifdef OMO_BRANCH_COUNTS
+            else if (nInRun) BC(BC_PASS_R_MUT_LAST_DOWN + !!dirIsUp);
+#endif
             if (lastPos == lRef) break;
             e = &pv[++iE];
         } else {                                                     /* O, M:3854-3873 */
@@ -223,6 +252,7 @@ int omo_passGenomeListThroughBranch(const OModel *m, const OEntry *pv, int n, co
             if (iM < lMut && mut[iM * 3] <= lastPos) {
                 OEntry ne = *e;
                 ne.x = dirIsUp ? mut[iM * 3 + 1] : mut[iM * 3 + 2];
+                BC((e->len > 3 ? BC_PASS_O_MUT_D0_DOWN : BC_PASS_O_MUT_DOWN) + !!dirIsUp);
                 iM++;
                 out[no++] = ne;
             } else out[no++] = *e;
@@ -909,29 +939,40 @@ int omo_areVectorsDifferent(const OModel *m, const OEntry *pv1, int n1, const OE
     const OEntry *e1 = &pv1[0], *e2 = &pv2[0];
     (void)n1;
     for (;;) {
-        if (e1->type != e2->type) return 1;
-        if (e1->len != e2->len) return 1;
+        if (e1->type != e2->type) { BC(BC_DIFFER_TYPE); return 1; }
+        if (e1->len != e2->len) { BC(BC_DIFFER_LEN); return 1; }
         if (e1->type < 5) {
             if (e1->len > 2) {
-                if (fabs(e1->d0 - e2->d0) > m->thresholdProb) return 1;
+                if (fabs(e1->d0 - e2->d0) > m->thresholdProb) { BC(BC_DIFFER_D0); return 1; }
                 if (e1->len > 3) {
                     /* element [3] is d1 (no error model, or len 5) or the flag (error model, len 4) */
                     double a3 = (U && e1->len == 4) ? (double)e1->flag : e1->d1;
                     double b3 = (U && e2->len == 4) ? (double)e2->flag : e2->d1;
-                    if (fabs(a3 - b3) > m->thresholdProb) return 1;
+                    if (fabs(a3 - b3) > m->thresholdProb) { BC((U && e1->len == 4) ? BC_DIFFER_FLAG4 : BC_DIFFER_D1); return 1; }
                     if (e1->len > 4) {
-                        if (fabs((double)e1->flag - (double)e2->flag) > m->thresholdProb) return 1;
+                        if (fabs((double)e1->flag - (double)e2->flag) > m->thresholdProb) { BC(BC_DIFFER_FLAG5); return 1; }
                     }
                 }
             }
             if (e1->type < 4) pos += 1;
             else pos = imin(e1->x, e2->x);
         } else if (e1->type == 6) {
-            if (e1->len == 4) { if (fabs(e1->d0 - e2->d0) > m->thresholdProb) return 1; }
+            if (e1->len == 4) { if (fabs(e1->d0 - e2->d0) > m->thresholdProb) { BC(BC_DIFFER_O_D0); return 1; } }
             for (int i = 0; i < 4; i++) {
                 double diffVal = fabs(e1->vec[i] - e2->vec[i]);
                 if (diffVal != 0.0) {
-                    if (e1->vec[i] == 0.0 || e2->vec[i] == 0.0) return 1;
+                    if (e1->vec[i] == 0.0 || e2->vec[i] == 0.0) { BC(BC_DIFFER_O_ZERO); return 1; }
+#ifdef OMO_BRANCH_COUNTS
+                    {
+                        const int q1 = diffVal / e1->vec[i] > m->thresholdFoldChangeUpdate;
+                        const int q2 = diffVal / e2->vec[i] > m->thresholdFoldChangeUpdate;
+                        if (diffVal > m->thresholdDiffForUpdate) BC(BC_DIFFER_O_ABS);
+                        else if (diffVal <= m->thresholdProb) BC(BC_DIFFER_O_SAME_THR);
+                        else if (q1 && !q2) BC(BC_DIFFER_O_FOLD_FIRST);
+                        else if (q2 && !q1) BC(BC_DIFFER_O_FOLD_SECOND);
+                        else if (!q1 && !q2) BC(BC_DIFFER_O_SAME_WINDOW);
+                    }
+#endif
                     if (diffVal > m->thresholdDiffForUpdate
                         || (diffVal > m->thresholdProb
                             && ((diffVal / e1->vec[i] > m->thresholdFoldChangeUpdate)
@@ -975,6 +1016,7 @@ int omo_rootVector(const OModel *m, const OEntry *pv, int n, double bLen, int is
             double nv[4], totSum = 0.0;
             double totBLen = bLen;
             if (e->len > 3) totBLen += e->d0;
+            BC((totBLen != 0.0 ? BC_ROOTVEC_O_LEN : BC_ROOTVEC_O_ZERO) + (e->len > 3));
             if (totBLen != 0.0) {
                 site_mat(m, newPos, M);
                 omo_getPartialVec(m, 6, totBLen, M, 0, e->vec, 0, 0, nv);
@@ -987,13 +1029,13 @@ int omo_rootVector(const OModel *m, const OEntry *pv, int n, double bLen, int is
         } else {
             if (U) {
                 int flag1 = ((e->len > 2) && e->flag) || isFromTip;
-                if (e->len > 3) b[no++] = mk(e->type, e->x, 5, e->d0 + bLen, 0.0, flag1);
-                else if (bLen != 0.0 || flag1) b[no++] = mk(e->type, e->x, 5, bLen, 0.0, flag1);
-                else b[no++] = mk(e->type, e->x, 2, 0, 0, 0);
+                if (e->len > 3) { BC(BC_ROOTVEC_ERR_TAIL); b[no++] = mk(e->type, e->x, 5, e->d0 + bLen, 0.0, flag1); }
+                else if (bLen != 0.0 || flag1) { BC(BC_ROOTVEC_ERR_BLEN); b[no++] = mk(e->type, e->x, 5, bLen, 0.0, flag1); }
+                else { BC(BC_ROOTVEC_ERR_BARE); b[no++] = mk(e->type, e->x, 2, 0, 0, 0); }
             } else {
-                if (e->len == 3) b[no++] = mk(e->type, e->x, 4, e->d0 + bLen, 0.0, 0);
-                else if (bLen != 0.0) b[no++] = mk(e->type, e->x, 4, bLen, 0.0, 0);
-                else b[no++] = mk(e->type, e->x, 2, 0, 0, 0);
+                if (e->len == 3) { BC(BC_ROOTVEC_PLAIN_TAIL); b[no++] = mk(e->type, e->x, 4, e->d0 + bLen, 0.0, 0); }
+                else if (bLen != 0.0) { BC(BC_ROOTVEC_PLAIN_BLEN); b[no++] = mk(e->type, e->x, 4, bLen, 0.0, 0); }
+                else { BC(BC_ROOTVEC_PLAIN_BARE); b[no++] = mk(e->type, e->x, 2, 0, 0, 0); }
             }
             if (e->type < 4) newPos += 1; else newPos = e->x;
         }
@@ -1034,8 +1076,9 @@ int omo_findProbRoot(const OModel *m, const OEntry *pv, int n, const int *mut3, 
     for (int k = 0; k < n; k++) {
         const OEntry *e = &a[k];
         if (U && e->type < 5 && e->len > 2 && e->flag) {
-            if (e->type == 4) { logLK += rflec[e->x] - rflec[pos]; pos = e->x; }
+            if (e->type == 4) { BC(BC_ROOTPROB_FLAG_R); logLK += rflec[e->x] - rflec[pos]; pos = e->x; }
             else {
+                BC(SS ? BC_ROOTPROB_FLAG_NUC_SITE : BC_ROOTPROB_FLAG_NUC_GLOBAL);
                 if (SS) errorRate = m->errorRates[pos];
                 logFactor *= (rf[e->type] * (1.0 - 1.33333 * errorRate) + 0.33333 * errorRate);
                 pos += 1;
@@ -1053,7 +1096,8 @@ int omo_findProbRoot(const OModel *m, const OEntry *pv, int n, const int *mut3, 
             } else pos = e->x;
         }
         if (logFactor <= m->minimumCarryOver) {
-            if (logFactor < DBL_MIN) { *outLK = -INFINITY; return 0; }
+            if (logFactor < DBL_MIN) { BC(BC_ROOTPROB_MINUS_INF); *outLK = -INFINITY; return 0; }
+            BC(BC_ROOTPROB_CARRY);
             logLK += log(logFactor);
             logFactor = 1.0;
         }

@@ -13,6 +13,12 @@
 #include <stdlib.h>
 #include <string.h>
 
+#ifdef OMO_BRANCH_COUNTS
+#include "maple_oracle_bc.h"        /* the counters of tests/test_list_edges_coverage.py; the default build has none */
+#else
+#define BC(k) ((void)0)
+#endif
+
 /* ---- a tiny arena of lists ------------------------------------------------------------------------------------- */
 typedef struct { OEntry *e; int n; } OL;          /* a genome list; e == NULL means the reference's None */
 
@@ -430,42 +436,44 @@ int omo_isMinorSequence(const OModel *m, const OEntry *pv1, int n1, const OEntry
     for (;;) {
         const OEntry *e1 = &pv1[i1], *e2 = &pv2[i2];
         if (e1->type != e2->type) {
-            if (onlyFindIdentical) return 0;
+            if (onlyFindIdentical) { BC(BC_MINOR_IDENTICAL_TYPE); return 0; }
             if (e1->type == 5) {
-                if (e2->type == 4) pos = e1->x < e2->x ? e1->x : e2->x;
-                else pos++;
+                if (e2->type == 4) { BC(BC_MINOR_N_R); pos = e1->x < e2->x ? e1->x : e2->x; }
+                else { BC(BC_MINOR_N_SITE); pos++; }
                 found2 = 1;
             } else if (e2->type == 5) {
-                if (e1->type == 4) pos = e1->x < e2->x ? e1->x : e2->x;
-                else pos++;
+                if (e1->type == 4) { BC(BC_MINOR_R_N); pos = e1->x < e2->x ? e1->x : e2->x; }
+                else { BC(BC_MINOR_SITE_N); pos++; }
                 found1 = 1;
             } else if (e1->type == 6) {
                 const int k = e2->type == 4 ? e1->x : e2->type;
-                if (e1->vec[k] > 0.1) found2 = 1;
-                else return 0;
+                if (e1->vec[k] > 0.1) { BC(BC_MINOR_O1_BIG); found2 = 1; }
+                else { BC(BC_MINOR_O1_SMALL); return 0; }
                 pos++;
             } else if (e2->type == 6) {
                 const int k = e1->type == 4 ? e2->x : e1->type;
-                if (e2->vec[k] > 0.1) found1 = 1;
-                else return 0;
+                if (e2->vec[k] > 0.1) { BC(BC_MINOR_O2_BIG); found1 = 1; }
+                else { BC(BC_MINOR_O2_SMALL); return 0; }
                 pos++;
-            } else return 0;
+            } else { BC(BC_MINOR_NUC_MISMATCH); return 0; }
         } else if (e1->type == 6) {
             for (int j = 0; j < 4; j++) {
                 if (onlyFindIdentical) {
-                    if (e2->vec[j] != e1->vec[j]) return 0;
-                } else if (e2->vec[j] > 0.1 && e1->vec[j] < 0.1) found1 = 1;
-                else if (e1->vec[j] > 0.1 && e2->vec[j] < 0.1) found2 = 1;
+                    if (e2->vec[j] != e1->vec[j]) { BC(BC_MINOR_OO_IDENTICAL_DIFF); return 0; }
+                    if (j == 3) BC(BC_MINOR_OO_IDENTICAL_SAME);
+                } else if (e2->vec[j] > 0.1 && e1->vec[j] < 0.1) { BC(BC_MINOR_OO_FOUND1); found1 = 1; }
+                else if (e1->vec[j] > 0.1 && e2->vec[j] < 0.1) { BC(BC_MINOR_OO_FOUND2); found2 = 1; }
             }
             pos++;
         } else if (e1->type < 4) pos++;
         else pos = e1->x < e2->x ? e1->x : e2->x;
-        if (found1 && found2) return 0;
+        if (found1 && found2) { BC(BC_MINOR_EARLY_BOTH); return 0; }
         if (pos == lRef) break;
         if (e1->type < 4 || e1->type == 6 || pos == e1->x) i1++;
         if (e2->type < 4 || e2->type == 6 || pos == e2->x) i2++;
         if (i1 >= n1 || i2 >= n2) return -1;                          /* the reference's IndexError */
     }
+    BC(found1 ? (found2 ? BC_MINOR_END_BOTH : BC_MINOR_END_1_BIGGER) : (found2 ? BC_MINOR_END_2_BIGGER : BC_MINOR_END_EQUAL));
     if (found1) return found2 ? 0 : 1;
     return found2 ? 2 : 1;
 }

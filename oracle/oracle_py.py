@@ -520,6 +520,14 @@ class Oracle:
                                   _p(t1), _p(t2), cap, C.byref(out))
         return out.value
 
+    def isMinorSequence(self, pv1, pv2, onlyFindIdentical=False):
+        """isMinorSequence(probVect1, probVect2, onlyFindIdentical), M:5918-6003: 0, 1 or 2."""
+        a, b = to_entries(pv1, self.u), to_entries(pv2, self.u)
+        r = self.lib.omo_isMinorSequence(C.byref(self.m), _p(a), len(a), _p(b), len(b), int(bool(onlyFindIdentical)))
+        if r < 0:
+            raise RuntimeError("isMinorSequence: a list ends before lRef")
+        return r
+
     # ---- batch driver for bench.py's cpu_baseline leg -------------------------------------------
     def pack_many(self, lists):
         arrs = [to_entries(gl, self.u) for gl in lists]

@@ -21,6 +21,23 @@ branch:
                     position 1 and at lRef, adjacent single-site entries, a tail-less R in front of an N run or of an R with
                     a tail, a list without any R entry
   long              lists longer than the dense kernel stages (> MAPLE_QLDS entries, chunks over MAPLE_LDS_CAPW/CAPA)
+
+`struct_corpus(mode)` gives the families of the structural operators (passGenomeListThroughBranch, shorten,
+areVectorsDifferent, rootVector, findProbRoot, isMinorSequence), one per group of counters of oracle/maple_oracle_bc.h:
+
+  shorten_runs      runs of adjacent R entries in every tail form: the run-head rule (a candidate is compared with the run's
+                    FIRST entry: d0 = a, a + 0.8 * thresholdProb, a + 1.6 * thresholdProb keeps two entries, a neighbour rule
+                    one), refusals on the flag alone, runs that straddle entry 64 and entry 128 of a list, a list of more
+                    than 512 entries
+  pass_edges        named shapes: a mutation at position 1 and at lRef, on the first / last site of an R run, on adjacent
+                    sites, three and more in one run, R runs with every tail form, N runs that skip mutations, nucleotides
+                    that become R or keep their type, O entries -- each in both directions
+  pass_random       rich lists of more than 64 entries against mutation lists of 1, 2 and several dozen mutations
+  differ_edges      a list against a copy changed in one place, one case per return of areVectorsDifferent, and the
+                    fold-change window of O components (`expect` holds the answer where it is known by construction)
+  rootvec           lower lists with paths of 0, 1 and 3 mutated branches, bLen 0 and > 0, both values of isFromTip
+  rootprob          root-frame lower lists: flagged R runs and nucleotides, several hundred O entries (carry-overs)
+  minor             pairs of tip-like lists for isMinorSequence: every arm of the type ladder on both sides, O against O
 """
 import numpy as np
 
@@ -423,3 +440,388 @@ def check_grammar(gl, L, u):
             else:
                 assert len(e) in (2, 3, 4) and not any(isinstance(x, bool) for x in e), e
     assert pos == L, (pos, L)
+
+
+# ---- the structural operators ---------------------------------------------------------------------------------------------
+THR = 1e-8                                                        # thresholdProb of the devices and oracles the tests make
+
+
+def tail_forms(u):
+    """The tail forms of the grammar as (d1?, flag) choices: a tail is (d0,) or (d0, d1), plus the flag under an error model."""
+    return [(False, False), (True, False)] + ([(False, True), (True, True)] if u else [])
+
+
+def prefix_sites(b, rng, k):
+    """k adjacent single-site entries at positions 1..k: the next entry is entry number k of the list."""
+    for p in range(1, k + 1):
+        b.nuc(p, other(rng, int(b.ref[p - 1])))
+    return b
+
+
+def fam_shorten_runs(rng, ref, u):
+    out = []
+    a = 1e-4
+    heads = {"far": (a, a + 0.8 * THR, a + 1.6 * THR),            # the third is within THR of its neighbour, not of the head
+             "back": (a, a + 0.8 * THR, a),                       # all within THR of the head
+             "swing": (a, a + 0.8 * THR, a - 0.8 * THR)}          # the third is outside THR of its neighbour, within of the head
+    for lead in (0, 5, 62, 63, 64, 126, 127):                     # entries in front of the run: it straddles entry 64 / 128
+        for (has1, flag) in tail_forms(u):
+            for name, ds in heads.items():
+                for on_d1 in ((False, True) if has1 else (False,)):
+                    b = prefix_sites(Builder(ref, u), rng, lead)
+                    for k, d in enumerate(ds):
+                        d0, d1 = (3e-4, d) if on_d1 else (d, (2e-4 if has1 else None))
+                        b.run(4, lead + 1 + 2 * k, lead + 2 + 2 * k, d0=d0, d1=d1, flag=flag)
+                    b.nuc(lead + 9, other(rng, int(ref[lead + 8])))
+                    out.append(dict(vec=b.done(), name=("head", lead, has1, flag, name, on_d1)))
+    if u:                                                         # refused on the flag alone, in the middle and at the head
+        for lead in (3, 63):
+            for has1 in (False, True):
+                for flags in ((False, True, False), (True, True, False), (False, False, False)):
+                    b = prefix_sites(Builder(ref, u), rng, lead)
+                    for k, f in enumerate(flags):
+                        b.run(4, lead + 1 + k, lead + 1 + k, d0=1e-4, d1=(2e-4 if has1 else None), flag=f)
+                    out.append(dict(vec=b.done(), name=("flag", lead, has1, flags)))
+    # tail-less runs, runs whose neighbours differ in form, and lists that shorten leaves alone
+    b = Builder(ref, u).run(4, 1, 10).run(4, 11, 20).run(4, 21, 30, d0=1e-4).run(4, 31, 40, d0=1e-4, d1=1e-4).run(4, 41, 50)
+    out.append(dict(vec=b.run(5, 51, 60).run(4, 61, 70).run(4, 71, 80).done(), name="forms"))
+    out.append(dict(vec=[(4, len(ref))], name="all_R"))
+    out.append(dict(vec=Builder(ref, u).run(4, 1, 700).done(), name="two_R"))
+    for k in range(6):
+        out.append(dict(vec=random_list(rng, ref, u, int(rng.integers(5, 90))), name="tip"))
+    # long runs with drifting lengths: every entry is within THR of its neighbour, the head moves on when the drift passes THR
+    for n_run, step in ((40, 0.3), (150, 0.15), (600, 0.4)):      # (600 entries: more than the wavefront form stages)
+        for (has1, flag) in tail_forms(u)[:2 if n_run == 600 else None]:
+            b = Builder(ref, u)
+            for k in range(n_run):
+                b.run(4, 2 * k + 1, 2 * k + 2, d0=a + k * step * THR, d1=(5e-4 if has1 else None), flag=flag and k % 50 != 49)
+            out.append(dict(vec=b.done(), name=("drift", n_run, has1, flag)))
+    return out
+
+
+def rich_list(rng, ref, u, mean_gap, d1=True, flags=True, n_runs=True):
+    """A list with every kind of entry: nucleotides and O vectors with and without tails, N runs, R runs with tails, some of
+    them adjacent.  d1=False gives the grammar of a lower list (no second length)."""
+    L = len(ref)
+    b = Builder(ref, u)
+    p = 1
+    while True:
+        p += int(rng.choice([0, 0, 1, int(rng.integers(1, 2 * mean_gap))]))
+        if p > L - 45:
+            break
+        kind = int(rng.integers(0, 6 if n_runs else 5))
+        d0 = [None, 0.0, 1e-5, 3e-4][int(rng.integers(0, 4))]
+        if kind in (3, 4) and d0 is None:
+            d0 = 2e-5                                             # (no tail-less R run next to another: shorten would join them)
+        dd1 = float(rng.choice([1e-5, 2e-4])) if (d1 and d0 is not None and rng.random() < 0.5) else None
+        fl = bool(flags and rng.random() < 0.5)
+        if kind in (0, 1):
+            b.nuc(p, other(rng, int(ref[p - 1])), d0=d0, d1=dd1, flag=fl)
+        elif kind == 2:
+            b.o(p, rng.dirichlet([1.0] * 4), d0=d0)
+        elif kind in (3, 4):
+            end = p + int(rng.integers(0, 30))
+            b.run(4, p, end, d0=d0, d1=dd1, flag=fl)
+            p = end
+        else:
+            end = p + int(rng.integers(0, 40))
+            b.run(5, p, end)
+            p = end
+        p += 1
+    return b.done()
+
+
+def sites_of(gl):
+    """[(position, entry)] of the single-site entries of a list."""
+    out, pos = [], 0
+    for e in gl:
+        if e[0] in (4, 5):
+            pos = e[1]
+        else:
+            pos += 1
+            out.append((pos, e))
+    return out
+
+
+def mutation(ref, p, up, other_nuc):
+    """(pos, from, to) of a branch whose frame on the list's side has the reference nucleotide at p."""
+    r = int(ref[p - 1])
+    return (p, other_nuc, r) if up else (p, r, other_nuc)
+
+
+def fam_pass_edges(rng, ref, u):
+    L = len(ref)
+    r = lambda p: int(ref[p - 1])                              # noqa: E731
+    out = []
+    for up in (False, True):
+        mut = lambda p, x=None: mutation(ref, p, up, other(rng, r(p)) if x is None else x)      # noqa: E731
+        add = lambda name, pv, ms: out.append(dict(pv=pv, mutations=sorted(ms), dirIsUp=up, name=(name, up)))  # noqa: E731
+        add("ends_all_R", [(4, L)], [mut(1), mut(L)])
+        add("ends_sites", Builder(ref, u).nuc(1, other(rng, r(1))).o(L, rng.dirichlet([1.0] * 4), d0=1e-4).done(), [mut(1), mut(L)])
+        add("ends_N", Builder(ref, u).run(5, 1, 3).run(5, L - 2, L).done(), [mut(1), mut(L)])
+        add("one_at_1", [(4, L)], [mut(1)])
+        add("one_at_lRef", Builder(ref, u).run(4, 1, 10, d0=1e-4).done(), [mut(L)])
+        for (has1, flag) in [(None, False)] + tail_forms(u):
+            tail = dict() if has1 is None else dict(d0=1e-4, d1=(2e-4 if has1 else None), flag=flag)
+            run = lambda: Builder(ref, u).nuc(99, other(rng, r(99))).run(4, 100, 140, **tail).nuc(141, other(rng, r(141)))  # noqa: E731
+            add(("R_first", has1, flag), run().done(), [mut(100)])
+            add(("R_last", has1, flag), run().done(), [mut(140)])
+            add(("R_first_last", has1, flag), run().done(), [mut(100), mut(140)])
+            add(("R_adjacent", has1, flag), run().done(), [mut(110), mut(111), mut(113)])
+            add(("R_all", has1, flag), run().done(), [mut(p) for p in range(100, 141)])
+            add(("R_many", has1, flag), run().done(), [mut(p) for p in (100, 101, 102, 120, 139, 140)])
+            add(("R_single_site", has1, flag), Builder(ref, u).run(4, 200, 200, **tail).run(4, 201, 201, d0=5e-4, flag=False).done(),
+                [mut(200), mut(201)])
+        add("N_skip", Builder(ref, u).run(5, 50, 60).run(5, 300, 400).run(5, L - 20, L).done(),
+            [mut(55)] + [mut(p) for p in (300, 301, 350, 400)] + [mut(L - 20), mut(L)])
+        add("N_edges", Builder(ref, u).run(5, 50, 60).done(), [mut(49), mut(50), mut(60), mut(61)])
+        for (has1, flag) in [(None, False)] + tail_forms(u):
+            tail = dict() if has1 is None else dict(d0=1e-4, d1=(2e-4 if has1 else None), flag=flag)
+            x, y = other(rng, r(500)), other(rng, r(502))
+            b = Builder(ref, u).nuc(500, x, **tail).nuc(501, other(rng, r(501)), **tail).nuc(502, y, **tail)
+            add(("nuc", has1, flag), b.done(), [mut(500, x), mut(502, other(rng, r(502), (y,)))])
+        add("O", Builder(ref, u).o(600, rng.dirichlet([1.0] * 4)).o(601, rng.dirichlet([1.0] * 4), d0=2e-4).o(602, rng.dirichlet([1.0] * 4)).done(),
+            [mut(600), mut(601)])
+    return out
+
+
+def fam_pass_random(rng, ref, u, n=24):
+    """Rich lists of more than 64 entries; half of the mutations fall on the lists' own single-site entries, and half of
+    those turn the nucleotide into the new reference."""
+    L = len(ref)
+    out = []
+    for k in range(n):
+        pv = rich_list(rng, ref, u, mean_gap=[6, 10, 25][k % 3])
+        up = bool(k % 2)
+        n_mut = [1, 2, 40, 70, 12, 3][k % 6]
+        own = sites_of(pv)
+        ms = {}
+        for j in rng.permutation(len(own))[: n_mut // 2]:
+            p, e = own[int(j)]
+            x = e[0] if (e[0] < 4 and rng.random() < 0.5) else other(rng, int(ref[p - 1]))
+            ms[p] = mutation(ref, p, up, x)
+        while len(ms) < n_mut:
+            p = int(rng.integers(1, L + 1))
+            ms.setdefault(p, mutation(ref, p, up, other(rng, int(ref[p - 1]))))
+        out.append(dict(pv=pv, mutations=[ms[p] for p in sorted(ms)], dirIsUp=up, name=("random", k)))
+    return out
+
+
+def o_pair(rng, x, y, at):
+    """Two normalised vectors whose component `at` is x and y; the other three share 1 - x and 1 - y in the same proportions."""
+    w = rng.dirichlet([1.0, 1.0, 1.0])
+    mk = lambda z: [z if i == at else float(w[i - (i > at)] * (1.0 - z)) for i in range(4)]    # noqa: E731
+    return mk(x), mk(y)
+
+
+# one O component against another under the device defaults (thresholdProb 1e-8, thresholdDiffForUpdate 1e-5,
+# thresholdFoldChangeUpdate 1.01): (x, y, different?)
+WINDOW = [(1e-6, 4e-6, True),          # fold change, by the first quotient only
+          (4e-6, 1e-6, True),          # ... by the second quotient only
+          (4e-6, 6e-6, False),         # inside the window, both quotients small
+          (1e-6, 1.005e-6, False),     # difference <= thresholdProb
+          (0.0, 1e-9, True),           # a zero component
+          (1e-9, 0.0, True),
+          (0.3, 0.30002, True),        # above thresholdDiffForUpdate
+          (0.3, 0.300009, False),      # below it, quotients small
+          (2e-8, 5e-8, True),          # just above thresholdProb, first quotient
+          (5e-8, 2e-8, True)]
+
+
+def replace_entry(gl, k, e):
+    return gl[:k] + [e] + gl[k + 1:]
+
+
+def fam_differ_edges(rng, ref, u):
+    out = []
+    base = rich_list(rng, ref, u, mean_gap=12)
+    add = lambda name, a, b, expect=None: out.append(dict(pv1=a, pv2=b, name=name, expect=expect))  # noqa: E731
+    add("equal", base, list(base), False)
+    for s_at in (3, 700, 1400):                                    # an O entry early, in the middle and late in the walk
+        for at in range(4):
+            for (x, y, diff) in WINDOW:
+                if s_at != 700 and at != 1:
+                    continue
+                v1, v2 = o_pair(rng, x, y, at)
+                d0 = None if at % 2 else 1e-4
+                n1 = other(rng, int(ref[s_at - 2]))
+                a = Builder(ref, u).nuc(s_at - 1, n1).o(s_at, v1, d0=d0).done()
+                b = Builder(ref, u).nuc(s_at - 1, n1).o(s_at, v2, d0=d0).done()
+                add(("window", s_at, at, x, y), a, b, diff)
+    # one entry of the base list changed in one place
+    idx = {}
+    for k, e in enumerate(base):
+        kind = (e[0] if e[0] >= 4 else 0, len(e))
+        idx.setdefault(kind, []).append(k)
+    for kind, ks in sorted(idx.items()):
+        for k in ks[:2]:
+            e = base[k]
+            t = e[0]
+            if t == 6:
+                if len(e) == 4:
+                    add(("O_d0_far", k), base, replace_entry(base, k, (6, e[1], e[2] + 2 * THR, e[3])), True)
+                    add(("O_d0_near", k), base, replace_entry(base, k, (6, e[1], e[2] + 0.5 * THR, e[3])), False)
+                    add(("O_len", k), base, replace_entry(base, k, (6, e[1], e[3])), True)
+                else:
+                    add(("O_len", k), base, replace_entry(base, k, (6, e[1], 1e-4, e[2])), True)
+                add(("O_to_nuc", k), base, replace_entry(base, k, (other(rng, e[1]), e[1])), True)
+                continue
+            if t == 5:
+                add(("N_to_R", k), base, replace_entry(base, k, (4, e[1])), True)
+                continue
+            if len(e) == 2:
+                add(("bare_to_tail", k), base, replace_entry(base, k, (t, e[1], 1e-4) + ((False,) if u else ())), True)
+                if t < 4:
+                    add(("nuc_type", k), base, replace_entry(base, k, (other(rng, e[1], (t,)), e[1])), True)
+                continue
+            add(("d0_far", k), base, replace_entry(base, k, e[:2] + (e[2] + 2 * THR,) + e[3:]), True)
+            add(("d0_near", k), base, replace_entry(base, k, e[:2] + (e[2] + 0.5 * THR,) + e[3:]), False)
+            if len(e) == 4 + u:
+                add(("d1_far", k), base, replace_entry(base, k, e[:3] + (e[3] - 2 * THR,) + e[4:]), True)
+                add(("d1_near", k), base, replace_entry(base, k, e[:3] + (e[3] + 0.5 * THR,) + e[4:]), False)
+                add(("len", k), base, replace_entry(base, k, e[:3] + e[4:]), True)
+            if u:
+                add(("flag", k), base, replace_entry(base, k, e[:-1] + (not e[-1],)), True)
+    # an R run cut in two: the same sites, other entries
+    k = next(k for k, e in enumerate(base) if e[0] == 4 and len(e) == 2 and e[1] - (base[k - 1][1] if k and base[k - 1][0] in (4, 5) else 0) > 3)
+    add("run_cut", base, base[:k] + [(5, base[k][1] - 2), base[k]] + base[k + 1:], True)
+    # two long lists (more than the wavefront form stages) that differ in their last entry only
+    a = prefix_sites(Builder(ref, u), rng, 600).done()
+    add("long_equal", a, list(a), False)
+    add("long_last", a, a[:-1] + [(5, len(ref))], True)
+    return out
+
+
+def path_mutations(rng, ref, n_branches, n_mut):
+    """Mutation lists of n_branches branches on the way up from a node whose frame is `ref`, at distinct positions."""
+    L = len(ref)
+    ps = rng.choice(np.arange(1, L + 1), size=n_branches * n_mut, replace=False)
+    out = []
+    for k in range(n_branches):
+        out.append(sorted(mutation(ref, int(p), True, other(rng, int(ref[int(p) - 1]))) for p in ps[k * n_mut:(k + 1) * n_mut]))
+    return out
+
+
+def fam_rootvec(rng, ref, u, n=30):
+    out = []
+    L = len(ref)
+    for k in range(n):
+        pv = rich_list(rng, ref, u, mean_gap=[8, 30][k % 2], d1=False)
+        if k % 5 == 0:                                             # O entries with a length of 0.0 of their own, at both ends
+            pv = Builder(ref, u).o(1, rng.dirichlet([1.0] * 4), d0=0.0).o(2, rng.dirichlet([1.0] * 4)).o(L, rng.dirichlet([1.0] * 4), d0=0.0).done()
+        n_br = [0, 1, 3][k % 3]
+        path = path_mutations(rng, ref, n_br, [1, 5, 20][(k // 3) % 3]) if n_br else []
+        if n_br and k % 4 == 0:                                    # mutations on the list's own sites, and a branch without any
+            taken = {m[0] for br in path for m in br}
+            own = [p for p, e in sites_of(pv) if p not in taken][:6]
+            path[0] = sorted(path[0] + [mutation(ref, p, True, other(rng, int(ref[p - 1]))) for p in own])
+            path.insert(1, [])
+        out.append(dict(pv=pv, bLen=[0.0, 1e-4][(k // 2) % 2], isFromTip=bool((k // 4) % 2), path=path, name=("rootvec", k)))
+    return out
+
+
+def fam_rootprob(rng, ref, u, n=24):
+    out = []
+    L = len(ref)
+    for k in range(n):
+        out.append(dict(pv=rich_list(rng, ref, u, mean_gap=[4, 10, 40][k % 3], d1=False), name=("rich", k)))
+    for k in range(4):                                             # several hundred O entries heavy on the rarest nucleotides:
+        b = Builder(ref, u)                                        # each factor is about 0.2, the product is carried over
+        for p in range(3, 3 + 2 * [420, 700][k % 2], 2):
+            v = rng.dirichlet([1.0] * 4) * 0.02
+            v[1] += 0.49
+            v[2] += 0.49
+            b.o(p, v, d0=(1e-4 if p % 3 == 0 else None))
+        out.append(dict(pv=b.done(), name=("carry_O", k)))
+    if u:                                                          # the same with flagged nucleotides and flagged runs between them
+        for k in range(2):
+            b = Builder(ref, u)
+            for p in range(2, L - 1, 2):
+                b.run(4, p - 1, p - 1, d0=1e-4, flag=True)
+                b.nuc(p, other(rng, int(ref[p - 1])), d0=0.0, flag=True)
+            out.append(dict(pv=b.done(), name=("carry_flag", k)))
+        out.append(dict(pv=Builder(ref, u).run(4, 1, L, d0=1e-4, flag=True).done(), name="all_flagged_R"))
+    out.append(dict(pv=[(4, L)], name="all_R"))
+    out.append(dict(pv=[(5, L)], name="all_N"))
+    return out
+
+
+def tip_list(rng, ref, u, n_sites, n_n, n_o):
+    """A sample's list: nucleotides, N runs and ambiguity vectors, no lengths."""
+    L = len(ref)
+    b = Builder(ref, u)
+    starts = np.sort(rng.choice(np.arange(1, L - 40, 45), size=n_sites + n_n + n_o, replace=False))
+    kinds = rng.permutation([0] * n_sites + [1] * n_n + [2] * n_o)
+    for p, kd in zip(starts, kinds):
+        p = int(p) + int(rng.integers(0, 3))
+        if kd == 0:
+            b.nuc(p, other(rng, int(ref[p - 1])))
+        elif kd == 1:
+            b.run(5, p, p + int(rng.integers(0, 30)))
+        else:
+            v = [0.0] * 4
+            i, j = rng.choice(4, size=2, replace=False)
+            v[int(i)] = v[int(j)] = 0.5
+            b.o(p, v)
+    return b.done()
+
+
+def fam_minor(rng, ref, u, n=16):
+    L = len(ref)
+    r = lambda p: int(ref[p - 1])                              # noqa: E731
+    out = []
+    add = lambda name, a, b: out.append(dict(pv1=a, pv2=b, name=name))   # noqa: E731
+    s = 400
+    x = other(rng, r(s))
+    y = other(rng, r(s), (x,))
+    z = next(i for i in range(4) if i not in (x, y, r(s)))
+    B = lambda: Builder(ref, u).nuc(100, other(np.random.default_rng(5), r(100)))    # noqa: E731
+    vec = lambda *big: [0.5 if i in big else 0.0 for i in range(4)]       # noqa: E731
+    shapes = {"R": B().done(), "N": B().run(5, s, s).done(), "N_run": B().run(5, s - 20, s + 20).done(), "x": B().nuc(s, x).done(),
+              "y": B().nuc(s, y).done(), "O_xr": B().o(s, vec(x, r(s))).done(), "O_xy": B().o(s, vec(x, y)).done(),
+              "O_yz": B().o(s, vec(y, z)).done(), "O_xr_again": B().o(s, vec(x, r(s))).done(),
+              "O_soft": B().o(s, [0.85 if i == x else 0.05 for i in range(4)]).done(),
+              "N_first": Builder(ref, u).run(5, 1, 30).done(), "N_last": B().run(5, L - 30, L).done(),
+              "site_last": B().nuc(L, other(rng, r(L))).done(), "O_last": B().o(L, vec(r(L), other(rng, r(L)))).done()}
+    for a in sorted(shapes):
+        for b in sorted(shapes):
+            add((a, b), shapes[a], shapes[b])
+    # one side bigger early and the other late (the early exit), or only at the last site (the returns after the loop)
+    add("both_bigger", B().run(5, 200, 210).done(), B().run(5, 900, 910).done())
+    add("both_bigger_O", B().o(s, vec(x, y)).run(5, 900, 910).done(), B().nuc(s, x).done())
+    for k in range(n):
+        a = tip_list(rng, ref, u, int(rng.integers(2, 12)), int(rng.integers(0, 4)), int(rng.integers(0, 3)))
+        bb = list(a)
+        if k % 4:                                                  # b = a with some sites masked: a is at least as informative
+            own = [(i, q) for i, (q, e) in zip([i for i, e in enumerate(a) if e[0] < 4 or e[0] == 6], sites_of(a))]
+            for j in rng.permutation(len(own))[: 1 + k % 3]:
+                i, q = own[int(j)]
+                bb[i] = (5, q)
+            bb = merge_n_runs(bb)
+        add(("derived", k), a, bb)
+        add(("random", k), a, tip_list(rng, ref, u, 3, 1, 1))
+    return out
+
+
+def merge_n_runs(gl):
+    """Join adjacent N entries (a list never has two in a row)."""
+    out = []
+    for e in gl:
+        if out and out[-1][0] == 5 and e[0] == 5:
+            out[-1] = e
+        else:
+            out.append(e)
+    return out
+
+
+STRUCT_FAMILIES = ("shorten_runs", "pass_edges", "pass_random", "differ_edges", "rootvec", "rootprob", "minor")
+
+
+def struct_corpus(mode):
+    """{family: [case dict]} of the structural operators for a mode (the five standard modes)."""
+    ref = reference()
+    u = bool(model(mode).get("usingErrorRate"))
+    rng = np.random.default_rng(300 + MODES.index(mode))
+    return {"shorten_runs": fam_shorten_runs(rng, ref, u), "pass_edges": fam_pass_edges(rng, ref, u),
+            "pass_random": fam_pass_random(rng, ref, u), "differ_edges": fam_differ_edges(rng, ref, u),
+            "rootvec": fam_rootvec(rng, ref, u), "rootprob": fam_rootprob(rng, ref, u), "minor": fam_minor(rng, ref, u)}

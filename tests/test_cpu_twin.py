@@ -13,8 +13,10 @@ import subprocess
 
 import pytest
 
+import list_edges as le
 import test_hip_parity as P
 import test_hip_search as S
+import test_hip_struct_edges as E
 from golden_util import load, model_args, ref_indices
 
 ORACLE = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle")
@@ -23,7 +25,7 @@ TWIN_EXPORTS = ["maple_abi_version", "maple_create", "maple_destroy", "maple_las
                 "maple_arena_mark", "maple_arena_release", "maple_arena_stats", "maple_mutations_upload", "maple_append_batch",
                 "maple_merge_batch", "maple_blen_batch", "maple_differ_batch", "maple_pass_branch_batch", "maple_shorten_batch",
                 "maple_root_vector_batch", "maple_root_prob_batch", "maple_evaluate_placement_batch", "maple_tree_upload",
-                "maple_spr_search_batch"]
+                "maple_spr_search_batch", "maple_minor_batch"]
 
 
 @pytest.fixture(scope="module")
@@ -55,9 +57,29 @@ def test_operator_parity_tests_pass_on_the_cpu_twin(twin, name):
     dev = twin_device(twin, f["context"])
     env = (f, dev, P.make_oracle(f))
     for body in (P.test_model_tables, P.test_appendProbNode, P.test_lists_update_keeps_ids_and_changes_contents, P.test_mergeVectors,
-                 P.test_estimateBranchLength, P.test_evaluatePlacement, P.test_rootVector, P.test_structural_functions,
+                 P.test_estimateBranchLength, P.test_evaluatePlacement, P.test_rootVector, P.test_findProbRoot, P.test_structural_functions,
                  P.test_appendProbNode_log_of_zero_is_minus_infinity, P.test_ops_mirror_reads_like_the_reference):
         body(env)
+    dev.close()
+
+
+@pytest.mark.parametrize("mode", E.STD_MODES)
+def test_structural_edge_tests_pass_on_the_cpu_twin(twin, mode):
+    """The bodies of tests/test_hip_struct_edges.py that need only the twin's exports, as uploaded (the twin has one form of
+    each operator and no candidate sets): this proves the corpus and the test harness where there is no GPU."""
+    from maple_amd.runtime import Device
+    from oracle.oracle_py import Oracle
+    dev = Device(le.reference(), le.ROOT_FREQS, lib=twin)
+    o = Oracle(le.reference(), le.ROOT_FREQS)
+    for x in (dev, o):
+        x.set_model(**le.model(mode))
+    fam = le.struct_corpus(mode)
+    E.check_pass(dev, o, fam, forms=False)
+    E.check_shorten(dev, o, fam, forms=False)
+    E.check_differ(dev, o, fam, forms=False)
+    E.check_rootvec(dev, o, fam)
+    E.check_rootprob(dev, o, fam)
+    E.check_minor(dev, o, fam, candset=False)
     dev.close()
 
 

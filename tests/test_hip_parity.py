@@ -214,6 +214,28 @@ def test_rootVector(env):
             assert lists_match(lists[k], tup(r["ret"]), REL), (lists[k], r["ret"])
 
 
+def test_findProbRoot(env):
+    """maple_root_prob_batch on every recorded findProbRoot call: the list is taken up to the root frame through the call's
+    mutated branches (maple_pass_branch_batch, node first), then scored."""
+    f, dev, o = env
+    total = 0
+    for mid, recs in by_model(f, "findProbRoot").items():
+        dev.set_model(**model_args(f["models"][mid]))
+        mark = dev.mark()
+        ids = dev.upload([tup(r["pv"]) for r in recs])
+        for k in range(max(len(r["pathMutations"]) for r in recs)):
+            sel = [i for i, r in enumerate(recs) if len(r["pathMutations"]) > k and r["pathMutations"][k]]
+            if sel:
+                mids = dev.upload_mutations([recs[i]["pathMutations"][k] for i in sel])
+                ids[sel] = dev.pass_branch_batch(ids[sel], mids, True)
+        got = dev.root_prob_batch(ids)
+        dev.release(mark)
+        for g, r in zip(got, recs):
+            assert close(float(g), r["ret"], REL), (g, r["ret"])
+        total += len(recs)
+    assert total > 30
+
+
 def _u_groups(f, fn):
     g = {}
     for rec in f["calls"][fn]:

@@ -1,17 +1,27 @@
 """Coverage gate on the oracle (CPU): the adversarial corpus of tests/list_edges.py must reach every rarely taken operator
-branch that oracle/maple_oracle.c counts when built with -DOMO_BRANCH_COUNTS.  The GPU tests of test_hip_list_edges.py
-compare the kernels with the oracle on the same corpus, so a branch the corpus stops reaching would silently drop out of
-them.
+branch that oracle/maple_oracle.c and oracle/maple_oracle_search.c count when built with -DOMO_BRANCH_COUNTS (the counters are
+listed in oracle/maple_oracle_bc.h).  The GPU tests of test_hip_list_edges.py and test_hip_struct_edges.py compare the kernels
+with the oracle on the same corpus, so a branch the corpus stops reaching would silently drop out of them.
 
 Not counted, because valid inputs cannot reach it: mergeVectors(isUpDown) with an O vector against N on the FIRST side and a
 total length of 0 (oracle `else memcpy(newVec, e1->vec ...)` after `if (isUpDown && ((e1->len == 4 && e1->d0 > 0) || bLen1
 != 0.0))`, M:4647-4656): the condition asks for d0 > 0 or bLen1 != 0, and the sum of two non-negative branch lengths of
 which one is not 0 is not 0.  Nor the length-3 error-model entry of M:4515-4516, marked unreachable in the reference.
+
+Counted, and asserted to stay at 0 (UNREACHABLE), because valid inputs cannot reach them:
+  rootprob_minus_inf  findProbRoot's exit through -inf (M:4905-4907).  The running product is reset to 1 whenever it is at most
+                      minimumCarryOver = DBL_MIN * 1e50, and one step multiplies it by sum(rootFreqs[i] * vec[i]) of a
+                      normalised O vector or by rootFreqs[i] * (1 - 1.33333 e) + 0.33333 e of a flagged nucleotide: at least
+                      min(rootFreqs) (1 - 1.33333 e), far above 1e-50.  No step takes it from above minimumCarryOver to below
+                      DBL_MIN.
+  minor_end_both      isMinorSequence's `return 0` after the loop (M:5996-5998).  found1bigger and found2bigger are tested
+                      together at the end of every step, the last one included, before the loop is left (M:5977-5978).
 """
 import ctypes as C
 import os
 import subprocess
 
+import numpy as np
 import pytest
 
 import list_edges as le
@@ -21,6 +31,27 @@ from oracle.oracle_py import HERE, Oracle
 # the counters the recorded golden calls (tests/golden/calls_*.json.gz) leave at 0
 GOLDEN_ZERO = {"append_R_d1_O", "append_nuc_d1_O", "append_carry3", "merge_carry", "merge_underflow", "merge_updown_N_err_d0",
                "blen_none_R_d1", "blen_none_R_flag", "blen_none_nuc_d1", "blen_early_tenth", "evalplace_top_fallback"}
+# ... and of the structural operators (the fixtures record no isMinorSequence call at all)
+GOLDEN_ZERO |= {
+    "differ_O_d0", "differ_O_zero", "differ_d1", "differ_flag4", "differ_flag5",
+    "minor_N_R", "minor_N_site", "minor_O1_big", "minor_O1_small", "minor_O2_big", "minor_O2_small",
+    "minor_OO_found1", "minor_OO_found2", "minor_OO_identical_diff", "minor_OO_identical_same",
+    "minor_R_N", "minor_early_both", "minor_end_1_bigger", "minor_end_2_bigger", "minor_end_both",
+    "minor_end_equal", "minor_identical_type", "minor_nuc_mismatch", "minor_site_N",
+    "pass_down_O_mut_d0", "pass_down_R_mut_adjacent", "pass_down_mut_at_1", "pass_down_mut_at_lRef",
+    "pass_up_N_skip_many", "pass_up_R_mut_adjacent", "pass_up_R_tail_len5", "pass_up_mut_at_1",
+    "pass_up_mut_at_lRef",
+    "rootprob_carry", "rootprob_flag_R", "rootprob_flag_nuc_global", "rootprob_flag_nuc_site",
+    "rootprob_minus_inf",
+    "rootvec_O_len_d0", "rootvec_O_zero_d0",
+    "shorten_head_near_neighbour_far", "shorten_refuse_head_far"}
+UNREACHABLE = {"rootprob_minus_inf", "minor_end_both"}
+PLAIN_ONLY = {"shorten_absorb_len3", "pass_down_R_tail_len3", "pass_up_R_tail_len3", "rootvec_plain_tail", "rootvec_plain_blen",
+              "rootvec_plain_bare"}                                # tuple forms and arms that exist only without an error model
+ERR_ONLY = {"shorten_absorb_len5", "shorten_refuse_flag", "pass_down_R_tail_len5", "pass_up_R_tail_len5", "differ_flag4",
+            "differ_flag5", "rootvec_err_tail", "rootvec_err_blen", "rootvec_err_bare", "rootprob_flag_R"}
+STRUCT_PREFIX = {"shorten_runs": ("shorten_",), "pass_edges": ("pass_",), "differ_edges": ("differ_",), "rootvec": ("rootvec_",),
+                 "rootprob": ("rootprob_",), "minor": ("minor_",)}
 
 
 @pytest.fixture(scope="module")
@@ -55,6 +86,21 @@ def run_case(o, fam, c):
     return o.evaluatePlacement(c["midTot"], c["down"], c["up"], c["distance"], c["rem"], c["isRemovedTip"], c["fromTip1"])
 
 
+def run_struct_case(o, fam, c):
+    """One case of the structural families through the oracle (both modes of isMinorSequence)."""
+    if fam == "shorten_runs":
+        return o.shorten(c["vec"])
+    if fam.startswith("pass"):
+        return o.passGenomeListThroughBranch(c["pv"], c["mutations"], c["dirIsUp"])
+    if fam == "differ_edges":
+        return o.areVectorsDifferent(c["pv1"], c["pv2"])
+    if fam == "rootvec":
+        return o.rootVector(c["pv"], c["bLen"], c["isFromTip"], c["path"])
+    if fam == "rootprob":
+        return o.findProbRoot(c["pv"], [])
+    return [o.isMinorSequence(c["pv1"], c["pv2"], f) for f in (False, True)]
+
+
 def test_corpus_follows_the_grammar():
     for mode in le.MODES:
         u = bool(le.model(mode).get("usingErrorRate"))
@@ -66,6 +112,71 @@ def test_corpus_follows_the_grammar():
         qs, cs = le.dense_lists(mode) if not mode.startswith("zeroq") else ([], [])
         for gl in qs + cs:
             le.check_grammar(gl, le.L_REF, u)
+    for mode in le.MODES[:5]:
+        u = bool(le.model(mode).get("usingErrorRate"))
+        for fam, cases in le.struct_corpus(mode).items():
+            assert len(cases) <= 240, (fam, len(cases))
+            for c in cases:
+                for k, v in c.items():
+                    if k in ("mutations", "path"):                 # mutation lists: sorted, positions unique and inside the genome
+                        for ml in ([v] if k == "mutations" else v):
+                            ps = [m[0] for m in ml]
+                            assert ps == sorted(set(ps)) and all(1 <= p <= le.L_REF for p in ps), (fam, c["name"])
+                            assert all(0 <= m[1] < 4 and 0 <= m[2] < 4 and m[1] != m[2] for m in ml)
+                    elif isinstance(v, list) and v and isinstance(v[0], tuple):
+                        le.check_grammar(v, le.L_REF, u)
+
+
+def test_struct_corpus_reaches_every_counted_branch(counting_lib):
+    """Every counter of the six structural operators is reached by its own family in every standard mode that can reach it;
+    the two that valid inputs cannot reach stay at 0.  The families also give both answers of areVectorsDifferent (the window
+    cases with the answer they are built to have), all three of isMinorSequence, and lists that shorten changes and leaves."""
+    o = Oracle(le.reference(), le.ROOT_FREQS, lib_path=counting_lib)
+    read_counts(o.lib)
+    for mode in le.MODES[:5]:
+        m = le.model(mode)
+        u, ss = bool(m.get("usingErrorRate")), m.get("errorRates") is not None
+        o.set_model(**m)
+        corp = le.struct_corpus(mode)
+        assert set(corp) == set(le.STRUCT_FAMILIES)
+        counts = {}
+        for fam, cases in corp.items():
+            res = [run_struct_case(o, fam, c) for c in cases]
+            counts[fam] = read_counts(o.lib)
+            if fam == "differ_edges":
+                assert all(c["expect"] is None or c["expect"] == r for c, r in zip(cases, res))
+                assert sum(c["expect"] is not None for c in cases) > 50 and {True, False} == set(res)
+            elif fam == "minor":
+                assert {r[0] for r in res} == {0, 1, 2} and {r[1] for r in res} == {0, 1}
+            elif fam == "shorten_runs":
+                changed = [r != c["vec"] for c, r in zip(cases, res)]
+                assert any(changed) and not all(changed)
+        for fam, prefixes in STRUCT_PREFIX.items():
+            got = dict(counts[fam])
+            for k, v in got.items():
+                if not k.startswith(prefixes):
+                    continue
+                cannot = (k in UNREACHABLE or (u and k in PLAIN_ONLY) or (not u and k in ERR_ONLY)
+                          or k == ("rootprob_flag_nuc_global" if (ss or not u) else "rootprob_flag_nuc_site")
+                          or (not u and k == "rootprob_flag_nuc_site"))
+                assert (v == 0) if cannot else (v > 0), (mode, fam, k, v)
+
+
+def test_run_head_rule_and_fold_change_window():
+    """The two inputs that tell a subtly wrong implementation from a right one, with the answers written out."""
+    o = Oracle(le.reference(), le.ROOT_FREQS)
+    L = le.L_REF
+    a, thr = 1e-4, le.THR
+    for mode in ("unrest", "gerr"):
+        o.set_model(**le.model(mode))
+        tail = (lambda d: (d, False)) if o.u else (lambda d: (d,))
+        run = lambda ds: [(4, 10)] + [(4, 11 + k) + tail(d) for k, d in enumerate(ds)] + [(4, L)]     # noqa: E731
+        far = o.shorten(run([a, a + 0.8 * thr, a + 1.6 * thr]))
+        assert far == [(4, 10), (4, 12) + tail(a + 0.8 * thr), (4, 13) + tail(a + 1.6 * thr), (4, L)]   # two kept, not one
+        assert o.shorten(run([a, a + 0.8 * thr, a])) == [(4, 10), (4, 13) + tail(a), (4, L)]
+        for x, y, want in le.WINDOW:
+            v1, v2 = le.o_pair(np.random.default_rng(0), x, y, 2)
+            assert o.areVectorsDifferent([(4, 5), (6, 1, v1), (4, L)], [(4, 5), (6, 1, v2), (4, L)]) == want, (x, y)
 
 
 def test_corpus_reaches_every_counted_branch(counting_lib):
@@ -83,7 +194,9 @@ def test_corpus_reaches_every_counted_branch(counting_lib):
                 per_family[k][f"{fam}/{mode}"] += v
     total = {k: sum(v.values()) for k, v in per_family.items()}
     print("\ncorpus branch counts:", total)
-    missing = sorted(k for k, v in total.items() if v == 0)
+    structural = tuple(x for pre in STRUCT_PREFIX.values() for x in pre)      # (test_struct_corpus_reaches_every_counted_branch)
+    assert len([k for k in total if not k.startswith(structural)]) == 12
+    missing = sorted(k for k, v in total.items() if v == 0 and not k.startswith(structural))
     assert not missing, f"the corpus no longer reaches {missing}"
     # each family reaches its own branch in every mode that can reach it
     aims = {"append_R_d1_O": "append_d1_O", "append_nuc_d1_O": "append_d1_O", "append_carry3": "append_carry",
@@ -124,6 +237,23 @@ def test_golden_calls_leave_these_branches_at_zero(counting_lib):
                 else:
                     o.evaluatePlacement(tup(r["midTot"]), tup(r["downVect"]), tup(r["upVect"]), r["distance"],
                                         tup(r["removedPartials"]), r["isRemovedTip"], r["fromTip1"])
+        Q = f["models"][0]["Q"]
+        for fn in ("passGenomeListThroughBranch", "shorten", "areVectorsDifferent"):
+            for r in f["calls"][fn]:
+                o.set_model(Q, usingErrorRate=bool(r["usingErrorRate"]), errorRateGlobal=1e-4)
+                if fn == "passGenomeListThroughBranch":
+                    o.passGenomeListThroughBranch(tup(r["pv"]), r["mutations"], r["dirIsUp"])
+                elif fn == "shorten":
+                    o.shorten(tup(r["vec"]))
+                else:
+                    o.areVectorsDifferent(tup(r["pv1"]), tup(r["pv2"]))
+        for fn in ("rootVector", "findProbRoot"):
+            for r in f["calls"][fn]:
+                o.set_model(**model_args(f["models"][r["model"]]))
+                if fn == "rootVector":
+                    o.rootVector(tup(r["pv"]), r["bLen"] or 0.0, r["isFromTip"], r["pathMutations"])
+                else:
+                    o.findProbRoot(tup(r["pv"]), r["pathMutations"])
         got = read_counts(o.lib)
         total = got if total is None else {k: total[k] + got[k] for k in got}
     zero = {k for k, v in total.items() if v == 0}

@@ -109,6 +109,17 @@ def test_rootVector(fx):
             assert lists_match(got, tup(r["ret"]), REL), (got, r["ret"])
 
 
+def test_findProbRoot(fx):
+    f, o = fx
+    n = 0
+    for mid, recs in by_model(f, "findProbRoot").items():
+        o.set_model(**model_args(f["models"][mid]))
+        for r in recs:
+            assert close(o.findProbRoot(tup(r["pv"]), r["pathMutations"]), r["ret"], REL), r["ret"]
+            n += 1
+    assert n > 30
+
+
 def _u_groups(f, fn):
     g = {}
     for rec in f["calls"][fn]:
