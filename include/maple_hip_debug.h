@@ -36,6 +36,11 @@ int maple_debug_calib_walk(maple_ctx *ctx, uint64_t bytes, int32_t repeats, floa
  * of a `bytes`-long buffer (the way the score matrix is written: bytes / 8 useful bytes). */
 int maple_debug_calib_write(maple_ctx *ctx, uint64_t bytes, int32_t mode, int32_t repeats, float *ms);
 int maple_debug_trace_read(maple_ctx *ctx, int32_t *n, int32_t *items4 /*[4*4096]*/, double *vals2 /*[2*4096]*/);
+/* What the library holds at this moment, process-wide (every context, no context needed): device and page-locked allocations
+ * and their bytes, and stream and event handles.  Kept by the types that own those resources, so a context that was destroyed
+ * has left nothing behind exactly if the three values are what they were before it was created.  Compare differences: two
+ * copies of the library in one process may share the counters. */
+int maple_debug_live_resources(int64_t *allocs, int64_t *bytes, int64_t *handles);
 /* Parity hooks for the two innermost device functions (one lane per call):
  * getPartialVec(i12, totLen, mutMatrix, errorRate, vect, upNode, flag), M:4073-4141, with the call's own 4x4 matrix
  * (M16[16*i..], row-major) and vect4[4*i..] (read when i12 == 6); whether `flag` matters follows the model's usingErrorRate

@@ -335,7 +335,7 @@ int launch_append_queries(maple_ctx *c, hipStream_t s, int nQ, const int32_t *qL
 {
     const long long tiles = (long long)nQ * (chunkTab ? nChunkTab : (nC + 63) / 64);
     if (tiles > 0x7fffffffLL - (1 << 20)) return fail(c, MAPLE_ERR_ARG, "nQ x nC too large for one launch");
-    if (!c->d_tile_counters) HIPCK(c, hipMalloc((void **)&c->d_tile_counters, 64 * sizeof(int32_t)));
+    HIPCK(c, c->d_tile_counters.reserve_exact(64));
     int32_t *counter = c->d_tile_counters + (c->tile_counter_next++ & 63);
     HIPCK(c, hipMemsetAsync(counter, 0, sizeof(int32_t), s));
     const long long waves = (tiles + 3) / 4;

@@ -65,15 +65,12 @@ static int stage_begin(maple_ctx *c, size_t bytes)
     c->stg_cur ^= 1;
     const int k = c->stg_cur;
     bytes += 4096;
-    if (bytes > c->stg_cap[k]) {
+    if (bytes > c->stg_d[k].cap) {
         HIPCK(c, hipStreamSynchronize(c->stream));
-        if (c->stg_h[k]) (void)hipHostFree(c->stg_h[k]);
-        if (c->stg_d[k]) (void)hipFree(c->stg_d[k]);
-        c->stg_h[k] = nullptr; c->stg_d[k] = nullptr; c->stg_cap[k] = 0;
+        c->stg_h[k].release(); c->stg_d[k].release();
         const size_t want = std::max(bytes * 2, (size_t)1 << 20);
-        HIPCK(c, hipHostMalloc((void **)&c->stg_h[k], want, hipHostMallocDefault));
-        HIPCK(c, hipMalloc((void **)&c->stg_d[k], want));
-        c->stg_cap[k] = want;
+        HIPCK(c, c->stg_h[k].reserve_exact(want));
+        HIPCK(c, c->stg_d[k].reserve_exact(want));
     }
     c->stg_used = c->stg_flushed = 0;
     return MAPLE_OK;
@@ -84,7 +81,7 @@ template <class T> static T *stage_put(maple_ctx *c, const T *src, size_t n)
 {
     const int k = c->stg_cur;
     const size_t off = (c->stg_used + 15) & ~(size_t)15, bytes = n * sizeof(T);
-    if (off + bytes > c->stg_cap[k]) return nullptr;
+    if (off + bytes > c->stg_d[k].cap) return nullptr;
     if (bytes) memcpy(c->stg_h[k] + off, src, bytes);
     c->stg_used = off + bytes;
     return (T *)(c->stg_d[k] + off);
@@ -139,9 +136,6 @@ __attribute__((visibility("hidden")))
 int launch_place_score(maple_ctx *c, int nQ, int nF, const int32_t *qFrameLists, int nC, const int32_t *cand, const int32_t *candFrame,
                        int isTip, double bLen, double *out, long long ldOut, const int32_t *outCol, const uint8_t *qTip, const double *qBLen,
                        int kind = MAPLE_K_PLACE_SCORE, double algBytes = 0.0);
-// ---- defined in update.hip -------------------------------------------------------------------------------------------------
-__attribute__((visibility("hidden")))
-void update_scratch_free(maple_ctx *c);
 // ---- defined in spr_batch.hip ----------------------------------------------------------------------------------------------
 // the device tree once more from the host copy of its columns (after maple_tree_patch left tables stale)
 __attribute__((visibility("hidden")))

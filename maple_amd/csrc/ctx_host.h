@@ -6,8 +6,10 @@
 #include "search_dev.h"
 #include "placement_dev.h"
 
+#include <atomic>
 #include <cstdarg>
 #include <cstdio>
+#include <memory>
 #include <string>
 #include <thread>
 #include <vector>
@@ -20,49 +22,120 @@ using namespace maple;
 typedef maple::ArenaViewS ArenaView;   // {words, aux, ent_off[], aux_off[], n_ent[], n_aux[]} per list
 typedef maple::MutViewS MutView;       // {mut3, off[], cnt[]} per mutation list
 
-struct DevBufStats { size_t allocs = 0, bytes = 0; };   // (for the verbose account of a call: what it had to allocate)
+// Ledger of what the owning types below hold at this moment, process-wide (maple_debug_live_resources); kept by them and nowhere
+// else.  Atomic: the library's own host thread (PlaceAhead::Spec) allocates too.
+struct DevBufStats {
+    size_t allocs = 0, bytes = 0;      // (for the verbose account of a call: what it had to allocate)
+    std::atomic<int64_t> live_allocs{0}, live_bytes{0};   // device and page-locked allocations together
+    std::atomic<int64_t> live_handles{0};                  // streams and events
+};
 inline DevBufStats &devbuf_stats() { static DevBufStats s; return s; }
-template <class T> struct DevBuf {     // grow-only device scratch
+inline void ledger_mem(int64_t allocs, int64_t bytes) { devbuf_stats().live_allocs += allocs; devbuf_stats().live_bytes += bytes; }
+
+// Every GPU resource of a context has one of these owners as a member: the destructor releases, copying is deleted (a copy would
+// free twice), moving hands the resource on.  An owner of nothing does nothing -- no runtime call -- and a destructor ignores
+// the runtime's status: it may run while the interpreter that loaded the library shuts down.  Kernels take `.p`, never the owner.
+template <class T> struct DevBuf {     // device memory; grow-only scratch (reserve) or allocated once (reserve_exact)
     T *p = nullptr;
-    size_t cap = 0;
-    hipError_t reserve(size_t n)
+    size_t cap = 0;                    // elements
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    DevBuf(DevBuf &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    DevBuf &operator=(DevBuf &&o) noexcept { if (this != &o) { release(); p = o.p; cap = o.cap; o.p = nullptr; o.cap = 0; } return *this; }
+    ~DevBuf() { release(); }
+    operator T *() const { return p; }
+    hipError_t reserve(size_t n) { return n <= cap ? hipSuccess : alloc(n + n / 2 + 64); }
+    hipError_t reserve_exact(size_t n) { return n <= cap ? hipSuccess : alloc(n); }   // for the very large buffers: no growth margin
+    void release()
     {
-        if (n <= cap) return hipSuccess;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        size_t want = n + n / 2 + 64;
+        if (p) { (void)hipFree(p); ledger_mem(-1, -(int64_t)(cap * sizeof(T))); }
+        p = nullptr; cap = 0;
+    }
+private:
+    hipError_t alloc(size_t want)
+    {
+        release();
         hipError_t e = hipMalloc((void **)&p, want * sizeof(T));
-        cap = (e == hipSuccess) ? want : 0;
+        if (e == hipSuccess) { cap = want; ledger_mem(1, (int64_t)(want * sizeof(T))); }
+        else p = nullptr;
         devbuf_stats().allocs++; devbuf_stats().bytes += want * sizeof(T);
         return e;
     }
-    hipError_t reserve_exact(size_t n)     // for the very large buffers: no growth margin
+};
+template <class T> struct PinArr {     // page-locked host memory of T, sized in BYTES (a D2H copy into pageable memory is staged by
+    T *p = nullptr, *dev = nullptr;    // the runtime at a few GB/s: 0.3 ms for the 1.6 MB of one query's scores); `dev`: the same
+    size_t cap = 0;                    // memory as the kernels address it, after map()
+    PinArr() = default;
+    PinArr(const PinArr &) = delete;
+    PinArr &operator=(const PinArr &) = delete;
+    PinArr(PinArr &&o) noexcept : p(o.p), dev(o.dev), cap(o.cap) { o.p = o.dev = nullptr; o.cap = 0; }
+    PinArr &operator=(PinArr &&o) noexcept
     {
-        if (n <= cap) return hipSuccess;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        hipError_t e = hipMalloc((void **)&p, n * sizeof(T));
-        cap = (e == hipSuccess) ? n : 0;
-        devbuf_stats().allocs++; devbuf_stats().bytes += n * sizeof(T);
+        if (this != &o) { release(); p = o.p; dev = o.dev; cap = o.cap; o.p = o.dev = nullptr; o.cap = 0; }
+        return *this;
+    }
+    ~PinArr() { release(); }
+    operator T *() const { return p; }
+    hipError_t reserve(size_t bytes) { return bytes <= cap ? hipSuccess : alloc(bytes + bytes / 2 + 4096); }
+    hipError_t reserve_exact(size_t bytes) { return bytes <= cap ? hipSuccess : alloc(bytes); }
+    hipError_t map()                   // zero copy: the device's address of this memory
+    {
+        void *d = nullptr;
+        hipError_t e = hipHostGetDevicePointer(&d, p, 0);
+        dev = (e == hipSuccess) ? (T *)d : nullptr;
         return e;
     }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-};
-struct PinBuf {                          // grow-only page-locked host scratch (a D2H copy into pageable memory is staged
-    void *p = nullptr;                  // by the runtime at a few GB/s: 0.3 ms for the 1.6 MB of one query's scores)
-    size_t cap = 0;
-    hipError_t reserve(size_t bytes)
+    void release()
     {
-        if (bytes <= cap) return hipSuccess;
-        if (p) (void)hipHostFree(p);
-        p = nullptr;
-        const size_t want = bytes + bytes / 2 + 4096;
-        hipError_t e = hipHostMalloc(&p, want, hipHostMallocDefault);
-        cap = (e == hipSuccess) ? want : 0;
+        if (p) { (void)hipHostFree(p); ledger_mem(-1, -(int64_t)cap); }
+        p = dev = nullptr; cap = 0;
+    }
+private:
+    hipError_t alloc(size_t want)
+    {
+        release();
+        hipError_t e = hipHostMalloc((void **)&p, want, hipHostMallocDefault);
+        if (e == hipSuccess) { cap = want; ledger_mem(1, (int64_t)want); }
+        else p = nullptr;
         return e;
     }
-    void release() { if (p) (void)hipHostFree(p); p = nullptr; cap = 0; }
 };
+typedef PinArr<void> PinBuf;
+
+struct Stream {
+    hipStream_t s = nullptr;
+    Stream() = default;
+    Stream(const Stream &) = delete;
+    Stream &operator=(const Stream &) = delete;
+    ~Stream() { if (s) { (void)hipStreamDestroy(s); devbuf_stats().live_handles--; } }
+    operator hipStream_t() const { return s; }
+    // non-blocking, optionally at a priority of the device's range; does nothing when the stream exists
+    hipError_t create(const int *priority = nullptr)
+    {
+        if (s) return hipSuccess;
+        hipError_t e = priority ? hipStreamCreateWithPriority(&s, hipStreamNonBlocking, *priority) : hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
+        if (e == hipSuccess) devbuf_stats().live_handles++; else s = nullptr;
+        return e;
+    }
+};
+struct Event {
+    hipEvent_t e = nullptr;
+    Event() = default;
+    Event(const Event &) = delete;
+    Event &operator=(const Event &) = delete;
+    Event(Event &&o) noexcept : e(o.e) { o.e = nullptr; }
+    ~Event() { if (e) { (void)hipEventDestroy(e); devbuf_stats().live_handles--; } }
+    operator hipEvent_t() const { return e; }
+    hipError_t create(unsigned flags = hipEventDefault)
+    {
+        if (e) return hipSuccess;
+        hipError_t r = hipEventCreateWithFlags(&e, flags);
+        if (r == hipSuccess) devbuf_stats().live_handles++; else e = nullptr;
+        return r;
+    }
+};
+struct ScratchBase { virtual ~ScratchBase() = default; };   // a unit's per-context scratch, its type private to the unit
 
 struct PlaceMeta {                     // derived from the uploaded tree, rebuilt when it or effectivelyNon0BLen changes
     bool valid = false;
@@ -90,6 +163,7 @@ struct PlaceMeta {                     // derived from the uploaded tree, rebuil
 // maple_placement_ahead: the score rows of the NEXT samples of a serial placement loop (M:11692-11752), made in one launch of
 // the batch kernel and kept current under maple_tree_patch -- see placement.hip
 struct PlaceAhead {
+    Stream copyStream, specStream;     // (first: destroyed after the buffers below)
     bool active = false;
     int32_t K = 0, next = 0;           // rows; the row the next single-query search takes
     std::vector<int32_t> q;            // the samples' list ids in the order they will be searched
@@ -99,14 +173,13 @@ struct PlaceAhead {
     // while the sample before it is being placed (hRow: two page-locked rows, taking turns), and what the placement in between
     // changed -- a handful of columns -- is patched into it from `hPatch`
     DevBuf<double> dTable;
-    double *hRow[3] = {nullptr, nullptr, nullptr}; size_t capRow = 0;    // doubles per row buffer (this sample's, the next one's -- a traversal
-                                       // made ahead may be reading it --, the one after that on its way)
+    PinArr<double> hRow[3];            // page-locked, all of one size (this sample's, the next one's -- a traversal made ahead may be
+                                       // reading it --, the one after that on its way)
     int32_t rowInBuf[3] = {-1, -1, -1};    // which row each buffer holds (or is receiving)
     int buf_of(int32_t row) const { for (int b = 0; b < 3; b++) if (rowInBuf[b] == row) return b; return -1; }
     int free_buf(int32_t keepA, int32_t keepB) const { for (int b = 0; b < 3; b++) if (rowInBuf[b] != keepA && rowInBuf[b] != keepB) return b; return -1; }
-    double *hPatch = nullptr, *dPatch = nullptr; size_t capPatch = 0;   // page-locked (bytes), written by the scoring launch of a search: the changed columns' scores, then the changed leaves' flags
-    void *hMinor = nullptr; uint8_t *dMinor = nullptr; size_t capMinor = 0;   // [K][ldL] u8 minor-sequence flags, page-locked, written by the kernel (1 MB per row)
-    hipStream_t copyStream = nullptr;
+    PinArr<double> hPatch;             // mapped, written by the scoring launch of a search: the changed columns' scores, then the changed leaves' flags
+    PinArr<uint8_t> hMinor;            // [K][ldL] u8 minor-sequence flags, mapped, written by the kernel (1 MB per row)
     int64_t ld = 0, ldL = 0;           // row strides: the columns at scoring time + room for what the placements add; [ld - 1] = the root vector's score
     DevBuf<int32_t> dQ, dCols, dLists;
     std::vector<int32_t> dirtyCols, dirtyLeaves;     // columns whose list changed (or that are new) since the rows were made: every search scores them for its sample
@@ -129,39 +202,26 @@ struct PlaceAhead {
     } spec;
     std::vector<int32_t> visitEpoch;   // per node: the epoch of the last speculative traversal that visited it
     int32_t specSeq = 0;
-    hipStream_t specStream = nullptr;
     DevBuf<int32_t> dSpecLists, dSpecLeaf;
-    double *hSpecPatch = nullptr, *dSpecPatch = nullptr; size_t capSpecPatch = 0;   // bytes
+    PinArr<double> hSpecPatch;         // mapped
     long long specUsed = 0, specDropped = 0;
     void join() { if (spec.th.joinable()) spec.th.join(); }
     DevBuf<uint8_t> dItems; DevBuf<unsigned long long> dCtr;
-    void release()
-    {
-        join();
-        if (hSpecPatch) (void)hipHostFree(hSpecPatch);
-        hSpecPatch = nullptr; dSpecPatch = nullptr; capSpecPatch = 0;
-        if (specStream) (void)hipStreamDestroy(specStream);
-        specStream = nullptr;
-        dSpecLists.release(); dSpecLeaf.release();
-        for (double *&r : hRow) { if (r) (void)hipHostFree(r); r = nullptr; }
-        if (hPatch) (void)hipHostFree(hPatch);
-        if (hMinor) (void)hipHostFree(hMinor);
-        if (copyStream) (void)hipStreamDestroy(copyStream);
-        hPatch = nullptr; dPatch = nullptr; hMinor = nullptr; dMinor = nullptr; copyStream = nullptr; capRow = capPatch = capMinor = 0;
-        dTable.release(); dQ.release(); dCols.release(); dLists.release(); dItems.release(); dCtr.release();
-        active = false;
-    }
+    ~PlaceAhead() { join(); }           // (in the body: a joinable std::thread must not reach its own destructor)
 };
 
 struct maple_ctx {
+    ~maple_ctx();                      // maple_hip.hip: quiesces and synchronises; the members below free themselves after it
     int device = 0;
-    hipStream_t stream = nullptr;
-    hipStream_t stream2 = nullptr;     // side stream: the dense scoring of the searches known to be whole-tree ones runs next to
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;   // the lane searches of the others (maple_spr_search_batch)
+    // (the streams come first: members are destroyed in reverse order, so buffers, then events and the units' scratch with their
+    // side streams, then these)
+    Stream stream;
+    Stream stream2;                    // side stream: the dense scoring of the searches known to be whole-tree ones runs next to
+    Event ev_fork, ev_join;            // the lane searches of the others (maple_spr_search_batch)
     DevBuf<int32_t> z_ql;
     DevBuf<uint8_t> z_qt;
     DevBuf<double> z_qb;
-    std::vector<hipEvent_t> evs;       // pairs (start, stop) of timed *_dev launches since the last reset
+    std::vector<Event> evs;            // pairs (start, stop) of timed *_dev launches since the last reset
     size_t ev_used = 0;
     // what each timed launch was: kind (MAPLE_K_*), units of work (pairs scored / searches run) and the algorithmic
     // bytes of SURVEY 8d for the scoring kernels
@@ -175,26 +235,26 @@ struct maple_ctx {
     int32_t lRef = 0;
     std::vector<uint8_t> refIdx;
     DevModel dm{};                     // device pointers inside
-    DevModel *d_model = nullptr;       // the same struct in device memory: what the kernels read
+    DevBuf<DevModel> d_model;          // the same struct in device memory: what the kernels read
     bool model_set = false;
-    double *d_siteRates = nullptr, *d_errorRates = nullptr, *d_cumRate = nullptr, *d_cumErr = nullptr;
-    int32_t *d_cumBases = nullptr;
-    double *d_rflec = nullptr;
+    DevBuf<double> d_siteRates, d_errorRates, d_cumRate, d_cumErr;
+    DevBuf<int32_t> d_cumBases;
+    DevBuf<double> d_rflec;
     std::vector<double> h_cumRate, h_cumErr;
     // list arena
-    uint2 *d_words = nullptr;
-    double *d_aux = nullptr;
+    DevBuf<uint2> d_words;
+    DevBuf<double> d_aux;
     int64_t cap_ent = 0, cap_aux = 0, cap_lists = 0;
     int64_t used_ent = 0, used_aux = 0;
-    int64_t *d_ent_off = nullptr, *d_aux_off = nullptr;
-    int32_t *d_n_ent = nullptr, *d_n_aux = nullptr;
+    DevBuf<int64_t> d_ent_off, d_aux_off;
+    DevBuf<int32_t> d_n_ent, d_n_aux;
     std::vector<int64_t> h_ent_off, h_aux_off;
     std::vector<int32_t> relocated;    // lists maple_lists_update moved to the end of the arena (maple_arena_release keeps their room)
     std::vector<int32_t> h_n_ent, h_n_aux;
     // mutation lists
-    int32_t *d_mut3 = nullptr;
-    int64_t *d_mut_off = nullptr;
-    int32_t *d_mut_cnt = nullptr;
+    DevBuf<int32_t> d_mut3;
+    DevBuf<int64_t> d_mut_off;
+    DevBuf<int32_t> d_mut_cnt;
     int64_t cap_mut = 0, used_mut = 0, cap_mut_lists = 0;
     std::vector<int64_t> h_mut_off;
     std::vector<int32_t> h_mut_cnt;
@@ -254,11 +314,11 @@ struct maple_ctx {
     DevBuf<uint8_t> s_search_out;
     DevBuf<int32_t> s_counter;
     DevBuf<double> s_cache;            // cached (query x node) scores of wide searches
-    struct CandSet { int32_t n = 0, nFrames = 0; int32_t *lists = nullptr, *frame = nullptr; };
+    struct CandSet { int32_t n = 0, nFrames = 0; DevBuf<int32_t> lists, frame; };
     std::vector<CandSet> candsets;     // resident candidate sets (maple_candset_create)
     // batched placement (maple_placement_search_batch)
-    PlaceMeta *place = nullptr;
-    PlaceAhead *ahead = nullptr;
+    std::unique_ptr<PlaceMeta> place;
+    std::unique_ptr<PlaceAhead> ahead;
     std::vector<int32_t> h_tree_c0, h_tree_c1, h_tree_mut, h_tree_totUp, h_tree_upRight, h_tree_upLeft;
     std::vector<NodeRec> h_nodes;      // host copy of the node records (host-side traversal of tiny placement batches)
     DevBuf<int32_t> p_i32[4];
@@ -268,13 +328,13 @@ struct maple_ctx {
     DevBuf<int16_t> p_i16;
     DevBuf<uint8_t> p_u8, p_minor;
     DevBuf<uint32_t> p_from;
-    int32_t *d_tile_counters = nullptr;    // ring of tile counters for the dynamically scheduled kernels
+    DevBuf<int32_t> d_tile_counters;       // ring of tile counters for the dynamically scheduled kernels
     int tile_counter_next = 0;
-    void *upd = nullptr;               // UpdateScratch of maple_update_partials (update.hip)
+    std::unique_ptr<ScratchBase> upd;  // UpdateScratch of maple_update_partials (update.hip)
     std::vector<SearchOut> h_search_out;   // per-search results of the last maple_spr_search_batch on the host (kept: 24 MB of fresh
                                        // pages per call cost 5 ms at 200 000 searches)
-    void *frontier = nullptr;          // FrontierScratch of the frontier tier of the SPR search (frontier.hip)
-    void *witness = nullptr;           // WitnessScratch of the whole-tree searches' candidate filter (witness.hip)
+    std::unique_ptr<ScratchBase> frontier;   // FrontierScratch of the frontier tier of the SPR search (frontier.hip)
+    std::unique_ptr<ScratchBase> witness;    // WitnessScratch of the whole-tree searches' candidate filter (witness.hip)
     bool last_search_frontier_only = false;   // maple_spr_search_visited can report on the last maple_spr_search_batch
     bool nodes_current = false;        // the node records of the SPR search on the device follow every maple_tree_patch
     bool tree_stale = false;           // maple_tree_patch changed the host copy of the tree; the device tables of the SPR search
@@ -282,8 +342,9 @@ struct maple_ctx {
     // Staging of the small per-call argument columns of the batch operators: they are gathered in pinned host memory and go
     // to the device in ONE copy per call (a dozen separate copies from pageable memory cost ~0.2 ms per call, most of a
     // single-change updatePartials).  Two arenas used in turn: see stage_begin.
-    uint8_t *stg_h[2] = {nullptr, nullptr}, *stg_d[2] = {nullptr, nullptr};
-    size_t stg_cap[2] = {0, 0}, stg_used = 0, stg_flushed = 0;
+    PinArr<uint8_t> stg_h[2];
+    DevBuf<uint8_t> stg_d[2];           // (of the same size as stg_h, allocated after it)
+    size_t stg_used = 0, stg_flushed = 0;
     int stg_cur = 0;
     bool commit_pending = false;       // commit_lists left its copy kernel running on `stream`: entry points that launch on a
                                        // caller's stream wait for it first (settle)

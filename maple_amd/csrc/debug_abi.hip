@@ -42,21 +42,19 @@ extern "C" int maple_debug_calib_write(maple_ctx *c, uint64_t bytes, int32_t mod
 {
     if (!c || bytes < 512 || repeats <= 0 || mode < 1 || mode > 2) return MAPLE_ERR_ARG;
     HIPCK(c, hipSetDevice(c->device));
-    unsigned long long *buf = nullptr;
-    HIPCK(c, hipMalloc((void **)&buf, bytes));
+    DevBuf<unsigned long long> buf;
+    HIPCK(c, buf.reserve_exact((size_t)((bytes + 7) / 8)));
     HIPCK(c, hipMemset(buf, 0, bytes));
     HIPCK(c, hipDeviceSynchronize());
-    hipEvent_t e0, e1;
-    HIPCK(c, hipEventCreate(&e0));
-    HIPCK(c, hipEventCreate(&e1));
+    Event e0, e1;
+    HIPCK(c, e0.create());
+    HIPCK(c, e1.create());
     HIPCK(c, hipEventRecord(e0, c->stream));
     for (int r = 0; r < repeats; r++)
-        hipLaunchKernelGGL(k_calib_write, dim3(4096), dim3(MAPLE_BLOCK), 0, c->stream, buf, (long long)(bytes / 8), mode == 1 ? 1 : 8);
+        hipLaunchKernelGGL(k_calib_write, dim3(4096), dim3(MAPLE_BLOCK), 0, c->stream, buf.p, (long long)(bytes / 8), mode == 1 ? 1 : 8);
     HIPCK(c, hipEventRecord(e1, c->stream));
     HIPCK(c, hipEventSynchronize(e1));
     if (ms) HIPCK(c, hipEventElapsedTime(ms, e0, e1));
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    (void)hipFree(buf);
     return MAPLE_OK;
 }
 
@@ -64,22 +62,20 @@ extern "C" int maple_debug_calib_walk(maple_ctx *c, uint64_t bytes, int32_t repe
 {
     if (!c || bytes < 512 || repeats <= 0) return MAPLE_ERR_ARG;
     HIPCK(c, hipSetDevice(c->device));
-    unsigned long long *buf = nullptr, *sink = nullptr;
-    HIPCK(c, hipMalloc((void **)&buf, bytes));
-    HIPCK(c, hipMalloc((void **)&sink, 8));
+    DevBuf<unsigned long long> buf, sink;
+    HIPCK(c, buf.reserve_exact((size_t)((bytes + 7) / 8)));
+    HIPCK(c, sink.reserve_exact(1));
     HIPCK(c, hipMemset(buf, 1, bytes));
     HIPCK(c, hipDeviceSynchronize());
-    hipEvent_t e0, e1;
-    HIPCK(c, hipEventCreate(&e0));
-    HIPCK(c, hipEventCreate(&e1));
+    Event e0, e1;
+    HIPCK(c, e0.create());
+    HIPCK(c, e1.create());
     HIPCK(c, hipEventRecord(e0, c->stream));
     for (int r = 0; r < repeats; r++)
-        hipLaunchKernelGGL(k_calib_walk, dim3(2048), dim3(MAPLE_BLOCK), 0, c->stream, buf, (long long)(bytes / 512), sink);
+        hipLaunchKernelGGL(k_calib_walk, dim3(2048), dim3(MAPLE_BLOCK), 0, c->stream, buf.p, (long long)(bytes / 512), sink.p);
     HIPCK(c, hipEventRecord(e1, c->stream));
     HIPCK(c, hipEventSynchronize(e1));
     if (ms) HIPCK(c, hipEventElapsedTime(ms, e0, e1));
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    (void)hipFree(buf); (void)hipFree(sink);
     return MAPLE_OK;
 }
 
@@ -179,6 +175,14 @@ extern "C" int maple_debug_wave_append_batch(maple_ctx *c, int32_t n, const int3
     HIPCK(c, hipMemcpyAsync(out, c->s_f64[1].p, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCK(c, hipStreamSynchronize(c->stream));
     if (ms) HIPCK(c, hipEventElapsedTime(ms, e0, e1));
+    return MAPLE_OK;
+}
+
+extern "C" int maple_debug_live_resources(int64_t *allocs, int64_t *bytes, int64_t *handles)
+{
+    if (!allocs || !bytes || !handles) return MAPLE_ERR_ARG;
+    const DevBufStats &s = devbuf_stats();
+    *allocs = s.live_allocs; *bytes = s.live_bytes; *handles = s.live_handles;
     return MAPLE_OK;
 }
 
@@ -294,8 +298,9 @@ extern "C" int maple_debug_frontier_pass_batch(maple_ctx *c, int32_t n, const in
                  oWoff = up16(oSa + (waveForm ? 0 : (size_t)lanes * 5 * capE * sizeof(double))), oAoff = up16(oWoff + (size_t)n * 8),
                  oHandle = up16(oAoff + (size_t)n * 8), oNe = up16(oHandle + (size_t)n * 4), oNa = up16(oNe + (size_t)n * 4),
                  oFlag = up16(oNa + (size_t)n * 4), oGrade = up16(oFlag + (size_t)n), total = up16(oGrade + (size_t)n);
-    uint8_t *buf = nullptr;
-    HIPCK(c, hipMalloc((void **)&buf, total));
+    DevBuf<uint8_t> own;
+    HIPCK(c, own.reserve_exact(total));
+    uint8_t *const buf = own.p;
     int rc = MAPLE_OK;
     std::vector<int32_t> handle(n);
     do {
@@ -333,6 +338,5 @@ extern "C" int maple_debug_frontier_pass_batch(maple_ctx *c, int32_t n, const in
         if (hipStreamSynchronize(c->stream) != hipSuccess) { rc = fail(c, MAPLE_ERR_HIP, "hipStreamSynchronize"); break; }
         for (int i = 0; i < n; i++) if (sameHandle[i]) outList[i] = list[i];
     } while (0);
-    (void)hipFree(buf);
     return rc;
 }

@@ -1091,7 +1091,11 @@ __global__ __launch_bounds__(FR_BLOCK) void k_fr_export(FPools fp, long long nU,
     }
 }
 
-struct FrontierScratch {
+struct FrontierScratch : ScratchBase {
+    // the two kernels of a level read disjoint items (they only meet in the pools' atomic counters): the cached-regime one runs
+    // on a stream of its own next to the updating one -- a level of the latter lasts as long as its slowest item, on a few lanes
+    Stream side, side2;                              // (side: the cached-regime launches; side2: the k_fr_pass kernels next to them)
+    Event evFork, evJoin, evFork2, evJoin2;         // (streams, then events, then buffers: destroyed in the reverse order)
     DevBuf<uint8_t> itemsU, itemsC, srch, recs, ctr;
     DevBuf<uint2> tw, sw, bw;
     DevBuf<double> ta, sa, sais, ba;
@@ -1110,34 +1114,10 @@ struct FrontierScratch {
     long long needU = 0, needC = 0, needL = 0, needW = 0, needA = 0, needM = 0;   // what the last call asked of the pools, and its searches
     bool lastOverflow = false;         // ... and whether one of them ran over
     FPools lastPools{};
-    // the two kernels of a level read disjoint items (they only meet in the pools' atomic counters): the cached-regime one runs
-    // on a stream of its own next to the updating one -- a level of the latter lasts as long as its slowest item, on a few lanes
     int capE = 0;                                    // entries of a per-lane scratch slab
-    hipStream_t side = nullptr, side2 = nullptr;     // (side: the cached-regime launches; side2: the k_fr_pass kernels next to them)
-    hipEvent_t evFork = nullptr, evJoin = nullptr, evFork2 = nullptr, evJoin2 = nullptr;
 };
 
 }  // namespace
-
-void frontier_scratch_free(maple_ctx *c)
-{
-    FrontierScratch *F = (FrontierScratch *)c->frontier;
-    if (!F) return;
-    F->itemsU.release(); F->itemsC.release(); F->srch.release(); F->recs.release(); F->ctr.release();
-    F->tw.release(); F->sw.release(); F->ta.release(); F->sa.release(); F->sais.release(); F->bw.release(); F->ba.release();
-    F->trec.release(); F->arec.release(); F->nodes.release(); F->out.release();
-    F->expQ.release(); F->expNode.release();
-    F->perm.release(); F->perm2.release(); F->perm3.release(); F->perm4.release(); F->tot.release(); F->lsize.release(); F->lpos.release(); F->lpar.release(); F->visit.release(); F->lvl.release(); F->vbase.release(); F->wideBr.release(); F->wideRow.release(); F->wideQ.release(); F->wideCtr.release(); F->passList.release(); F->passListR.release(); F->deferred.release(); F->overHint.release(); F->bw2.release(); F->ba2.release(); F->tflag.release();
-    if (F->evFork) (void)hipEventDestroy(F->evFork);
-    if (F->evJoin) (void)hipEventDestroy(F->evJoin);
-    if (F->evFork2) (void)hipEventDestroy(F->evFork2);
-    if (F->evJoin2) (void)hipEventDestroy(F->evJoin2);
-    if (F->side) (void)hipStreamDestroy(F->side);
-    if (F->side2) (void)hipStreamDestroy(F->side2);
-    delete F;
-    c->frontier = nullptr;
-}
-
 
 // Runs the searches nodes[0..m) through the frontier tier; out[k] as k_spr_search leaves it: status 0 / 1 / 2 / -1 final,
 // -5 = over `budget` expanded items (dense tier), FR_STATUS_FALLBACK = hand to the one-lane-per-search kernel.
@@ -1145,8 +1125,8 @@ int frontier_search(maple_ctx *c, const SearchParams &P, int m, const int32_t *n
                     uint2 *poolW, double *poolA, unsigned long long *poolUsed, long long poolCapW, long long poolCapA,
                     FrontierStats *stats, long long itemsHint, const FrontierWide *wide, const uint8_t *overHint)
 {
-    if (!c->frontier) c->frontier = new FrontierScratch();
-    FrontierScratch &F = *(FrontierScratch *)c->frontier;
+    if (!c->frontier) c->frontier.reset(new FrontierScratch());
+    FrontierScratch &F = *static_cast<FrontierScratch *>(c->frontier.get());
     if (budget < 1) budget = 1 << 30;
     const auto tEnter = std::chrono::steady_clock::now();
     auto sinceEnter = [&] { return std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - tEnter).count() * 1e-3; };
@@ -1154,7 +1134,7 @@ int frontier_search(maple_ctx *c, const SearchParams &P, int m, const int32_t *n
     // pools, sized for the batch and bounded by what the device has free
     size_t freeB = 0, totalB = 0;
     if (hipMemGetInfo(&freeB, &totalB) != hipSuccess) freeB = (size_t)8 << 30;
-    const DevBufStats allocs0 = devbuf_stats();
+    const size_t allocs0 = devbuf_stats().allocs, allocBytes0 = devbuf_stats().bytes;
     struct PoolCap { const char *name; const size_t *cap; size_t elem, before; };
     PoolCap poolCaps[] = {{"itemsU", &F.itemsU.cap, 1, 0}, {"itemsC", &F.itemsC.cap, 1, 0}, {"tw", &F.tw.cap, 8, 0}, {"ta", &F.ta.cap, 8, 0},
                           {"trec", &F.trec.cap, 16, 0}, {"sw", &F.sw.cap, 8, 0}, {"sa", &F.sa.cap, 8, 0}, {"sais", &F.sais.cap, 8, 0},
@@ -1294,7 +1274,7 @@ int frontier_search(maple_ctx *c, const SearchParams &P, int m, const int32_t *n
         fp.deferred = F.deferred.p; fp.capDeferred = (long long)F.deferred.cap;
     }
     if (dbgTime) fprintf(stderr, "[maple]   frontier +%.1f ms: pools reserved (%zu allocations, %.2f GB; free %.1f GB, room %.1f GB; per-lane scratch %lld x %d entries, shared %lld + %lld)\n", sinceEnter(),
-                         devbuf_stats().allocs - allocs0.allocs, 1e-9 * (double)(devbuf_stats().bytes - allocs0.bytes), 1e-9 * (double)freeB, 1e-9 * room,
+                         devbuf_stats().allocs - allocs0, 1e-9 * (double)(devbuf_stats().bytes - allocBytes0), 1e-9 * (double)freeB, 1e-9 * room,
                          scratchLanes + extraSlabs, capE, capBig, capBig2);
     if (dbgTime)
         for (const PoolCap &pc : poolCaps)
@@ -1377,13 +1357,13 @@ int frontier_search(maple_ctx *c, const SearchParams &P, int m, const int32_t *n
         {
             int prLow = 0, prHigh = 0;
             if (hipDeviceGetStreamPriorityRange(&prLow, &prHigh) != hipSuccess) prLow = 0;
-            HIPCK(c, hipStreamCreateWithPriority(&F.side, hipStreamNonBlocking, prLow));
-            HIPCK(c, hipStreamCreateWithPriority(&F.side2, hipStreamNonBlocking, prLow));
+            HIPCK(c, F.side.create(&prLow));
+            HIPCK(c, F.side2.create(&prLow));
         }
-        HIPCK(c, hipEventCreateWithFlags(&F.evFork2, hipEventDisableTiming));
-        HIPCK(c, hipEventCreateWithFlags(&F.evJoin2, hipEventDisableTiming));
-        HIPCK(c, hipEventCreateWithFlags(&F.evFork, hipEventDisableTiming));
-        HIPCK(c, hipEventCreateWithFlags(&F.evJoin, hipEventDisableTiming));
+        HIPCK(c, F.evFork2.create(hipEventDisableTiming));
+        HIPCK(c, F.evJoin2.create(hipEventDisableTiming));
+        HIPCK(c, F.evFork.create(hipEventDisableTiming));
+        HIPCK(c, F.evJoin.create(hipEventDisableTiming));
     }
     const hipStream_t s2 = F.side, s3 = F.side2;
     // The two kinds of items run on two streams that never wait for each other inside the expansion: the list-updating levels
@@ -1636,7 +1616,7 @@ int frontier_search(maple_ctx *c, const SearchParams &P, int m, const int32_t *n
 // overflowed, MAPLE_ERR_ARG if they do not fit in cap)
 int frontier_export(maple_ctx *c, long long cap, int32_t *q, int32_t *node, long long *n)
 {
-    FrontierScratch *F = (FrontierScratch *)c->frontier;
+    FrontierScratch *F = static_cast<FrontierScratch *>(c->frontier.get());
     if (!F || F->lastU < 0) return fail(c, MAPLE_ERR_STATE, "no complete frontier search to export");
     const long long tot = F->lastU + F->lastC + F->lastR;
     *n = tot;
@@ -1657,7 +1637,7 @@ int frontier_export(maple_ctx *c, long long cap, int32_t *q, int32_t *node, long
 int frontier_level_profile(maple_ctx *c, int cap, long long *itemsU, long long *itemsC, float *msU, float *msC, int *n, long long *waveSmall,
                            long long *waveBig)
 {
-    FrontierScratch *F = (FrontierScratch *)c->frontier;
+    FrontierScratch *F = static_cast<FrontierScratch *>(c->frontier.get());
     if (!F) return fail(c, MAPLE_ERR_STATE, "no frontier search to report on");
     const int nl = (int)(F->lastLvl.size() / FR_LVL);
     *n = nl;

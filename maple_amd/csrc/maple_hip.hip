@@ -567,7 +567,7 @@ extern "C" int maple_create(maple_ctx **out, int device, int32_t lRef, const uin
         return MAPLE_ERR_HIP;          // no GPU: the product path fails loudly, there is no CPU fallback
     }
     if (hipSetDevice(device) != hipSuccess) { delete c; return MAPLE_ERR_HIP; }
-    if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) { delete c; return MAPLE_ERR_HIP; }
+    if (c->stream.create() != hipSuccess) { delete c; return MAPLE_ERR_HIP; }
     c->lRef = lRef;
     c->refIdx.assign(refIdx, refIdx + lRef);
     c->params = *params;
@@ -591,19 +591,23 @@ extern "C" int maple_create(maple_ctx **out, int device, int32_t lRef, const uin
     c->cap_lists = c->cap_ent / 4 + 1024;
     c->cap_mut = c->cap_ent / 16 + 4096;
     c->cap_mut_lists = c->cap_lists / 4 + 1024;
-    bool ok = hipMalloc((void **)&c->d_words, (c->cap_ent + 64) * sizeof(uint2)) == hipSuccess
-              && hipMalloc((void **)&c->d_aux, c->cap_aux * sizeof(double)) == hipSuccess
-              && hipMalloc((void **)&c->d_ent_off, c->cap_lists * sizeof(int64_t)) == hipSuccess
-              && hipMalloc((void **)&c->d_aux_off, c->cap_lists * sizeof(int64_t)) == hipSuccess
-              && hipMalloc((void **)&c->d_n_ent, c->cap_lists * sizeof(int32_t)) == hipSuccess
-              && hipMalloc((void **)&c->d_n_aux, c->cap_lists * sizeof(int32_t)) == hipSuccess
-              && hipMalloc((void **)&c->d_mut3, c->cap_mut * 3 * sizeof(int32_t)) == hipSuccess
-              && hipMalloc((void **)&c->d_mut_off, c->cap_mut_lists * sizeof(int64_t)) == hipSuccess
-              && hipMalloc((void **)&c->d_mut_cnt, c->cap_mut_lists * sizeof(int32_t)) == hipSuccess
-              && hipMalloc((void **)&c->d_cumRate, (lRef + 1) * sizeof(double)) == hipSuccess
-              && hipMalloc((void **)&c->d_model, sizeof(DevModel)) == hipSuccess;
-    ok = ok && hipMalloc((void **)&c->d_cumBases, (size_t)(lRef + 1) * 4 * sizeof(int32_t)) == hipSuccess;
-    if (!ok) { maple_destroy(c); return MAPLE_ERR_NOMEM; }
+    bool ok = c->d_words.reserve_exact(c->cap_ent + 64) == hipSuccess
+              && c->d_aux.reserve_exact(c->cap_aux) == hipSuccess
+              && c->d_ent_off.reserve_exact(c->cap_lists) == hipSuccess
+              && c->d_aux_off.reserve_exact(c->cap_lists) == hipSuccess
+              && c->d_n_ent.reserve_exact(c->cap_lists) == hipSuccess
+              && c->d_n_aux.reserve_exact(c->cap_lists) == hipSuccess
+              && c->d_mut3.reserve_exact(c->cap_mut * 3) == hipSuccess
+              && c->d_mut_off.reserve_exact(c->cap_mut_lists) == hipSuccess
+              && c->d_mut_cnt.reserve_exact(c->cap_mut_lists) == hipSuccess
+              && c->d_cumRate.reserve_exact(lRef + 1) == hipSuccess
+              && c->d_model.reserve_exact(1) == hipSuccess;
+    ok = ok && c->d_cumBases.reserve_exact((size_t)(lRef + 1) * 4) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();       // (the status reports the refused request: left behind as the thread's last error, the next
+        maple_destroy(c);              // launch check of another context would find it)
+        return MAPLE_ERR_NOMEM;
+    }
     {                                                                  // cumulativeBases, M:3669-3674
         std::vector<int32_t> cb((size_t)(lRef + 1) * 4, 0);
         for (int i = 0; i < lRef; i++) {
@@ -634,50 +638,21 @@ extern "C" int maple_set_tuning(maple_ctx *c, const maple_tuning *t)
     return MAPLE_OK;
 }
 
+// What cannot be left to the members, before any of them goes: the library's own thread reads what they free, and nothing may be
+// in flight on any stream of the context (the frontier tier's side streams live in its scratch: the device-wide wait).
+maple_ctx::~maple_ctx()
+{
+    ahead_quiesce(this);
+    if (!stream) return;                                                // (maple_create gave up before it had a device)
+    (void)hipSetDevice(device);
+    (void)hipStreamSynchronize(stream);
+    if (stream2) (void)hipStreamSynchronize(stream2);
+    (void)hipDeviceSynchronize();
+    if (rccl_comm && g_rccl.CommDestroy) (void)g_rccl.CommDestroy((ncclComm_t)rccl_comm);
+}
+
 extern "C" int maple_destroy(maple_ctx *c)
 {
-    if (!c) return MAPLE_OK;
-    ahead_quiesce(c);                                                   // (the library's own thread reads what is freed below)
-    // this context's device first, and nothing in flight on any of its streams, before anything is freed
-    (void)hipSetDevice(c->device);
-    if (c->stream) (void)hipStreamSynchronize(c->stream);
-    if (c->stream2) (void)hipStreamSynchronize(c->stream2);
-    (void)hipDeviceSynchronize();                                       // (the frontier tier's side stream lives in its scratch)
-    update_scratch_free(c);
-    frontier_scratch_free(c);
-    witness_scratch_free(c);
-    for (int k = 0; k < 2; k++) { if (c->stg_h[k]) (void)hipHostFree(c->stg_h[k]); if (c->stg_d[k]) (void)hipFree(c->stg_d[k]); }
-    void *ptrs[] = {c->d_cumBases, c->d_rflec, c->d_model, c->d_words, c->d_aux, c->d_ent_off, c->d_aux_off, c->d_n_ent, c->d_n_aux, c->d_mut3, c->d_mut_off,
-                    c->d_mut_cnt, c->d_cumRate, c->d_cumErr, c->d_siteRates, c->d_errorRates};
-    for (void *p : ptrs) if (p) (void)hipFree(p);
-    for (auto &b : c->s_i32) b.release();
-    for (auto &b : c->s_f64) b.release();
-    for (auto &b : c->s_u8) b.release();
-    for (auto &b : c->s_i64) b.release();
-    c->s_words.release(); c->s_aux.release(); c->s_ais.release(); c->s_pool_w.release(); c->s_pool_a.release();
-    for (auto &b : c->t_i32) b.release();
-    c->t_dist.release(); c->t_tip.release(); c->t_nodes.release(); c->t_scored_col.release(); c->t_scored_frame.release(); c->t_cand_rank.release(); c->s_cand_root.release(); c->s_frame_parent.release(); c->s_frame_node.release(); c->t_scan.release(); c->t_scan_parent.release(); c->t_cand_before.release(); c->t_clade_visits.release(); c->s_fin_mask.release(); c->s_fin_prefix.release(); c->s_tilebest.release(); c->s_comm_u64.release();
-    if (c->d_tile_counters) (void)hipFree(c->d_tile_counters);
-    c->s_search_ws.release(); c->s_search_ws_big.release(); c->s_search_out.release(); c->s_counter.release(); c->s_cache.release();
-    for (auto &b : c->p_i32) b.release();
-    for (auto &b : c->p_f64) b.release();
-    c->pin_place.release(); c->pin_res.release();
-    c->p_score.release(); c->p_i16.release(); c->p_u8.release(); c->p_minor.release(); c->p_from.release();
-    if (c->place) {
-        PlaceMeta &M = *c->place;
-        M.d_scan.release(); M.d_frameOf.release(); M.d_candIdx.release(); M.d_leafIdx.release(); M.d_candList.release(); M.d_candFrame.release();
-        M.d_leafList.release(); M.d_leafFrame.release(); M.d_pn.release();
-        delete c->place;
-    }
-    if (c->ahead) { c->ahead->release(); delete c->ahead; }
-    for (hipEvent_t e : c->evs) (void)hipEventDestroy(e);
-    for (auto &cs : c->candsets) { if (cs.lists) (void)hipFree(cs.lists); if (cs.frame) (void)hipFree(cs.frame); }
-    if (c->rccl_comm && g_rccl.CommDestroy) (void)g_rccl.CommDestroy((ncclComm_t)c->rccl_comm);
-    if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
-    if (c->ev_join) (void)hipEventDestroy(c->ev_join);
-    if (c->stream2) (void)hipStreamDestroy(c->stream2);
-    c->z_ql.release(); c->z_qt.release(); c->z_qb.release();
-    if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
     return MAPLE_OK;
 }
@@ -706,7 +681,7 @@ extern "C" int maple_set_model(maple_ctx *c, const double *Q16, const double *si
     HIPCK(c, hipMemcpyAsync(c->d_cumRate, c->h_cumRate.data(), (lRef + 1) * sizeof(double), hipMemcpyHostToDevice, c->stream));
     m.cumulativeRate = c->d_cumRate;
     if (siteRates) {
-        if (!c->d_siteRates) HIPCK(c, hipMalloc((void **)&c->d_siteRates, lRef * sizeof(double)));
+        HIPCK(c, c->d_siteRates.reserve_exact(lRef));
         HIPCK(c, hipMemcpyAsync(c->d_siteRates, siteRates, lRef * sizeof(double), hipMemcpyHostToDevice, c->stream));
         m.siteRates = c->d_siteRates;
     } else m.siteRates = nullptr;
@@ -720,8 +695,8 @@ extern "C" int maple_set_model(maple_ctx *c, const double *Q16, const double *si
             c->h_cumErr.assign(lRef + 1, 0.0);
             for (int i = 0; i < lRef; i++) c->h_cumErr[i + 1] = c->h_cumErr[i] + errorRates[i];
             m.totError = -c->h_cumErr[lRef];
-            if (!c->d_errorRates) HIPCK(c, hipMalloc((void **)&c->d_errorRates, lRef * sizeof(double)));
-            if (!c->d_cumErr) HIPCK(c, hipMalloc((void **)&c->d_cumErr, (lRef + 1) * sizeof(double)));
+            HIPCK(c, c->d_errorRates.reserve_exact(lRef));
+            HIPCK(c, c->d_cumErr.reserve_exact(lRef + 1));
             HIPCK(c, hipMemcpyAsync(c->d_errorRates, errorRates, lRef * sizeof(double), hipMemcpyHostToDevice, c->stream));
             HIPCK(c, hipMemcpyAsync(c->d_cumErr, c->h_cumErr.data(), (lRef + 1) * sizeof(double), hipMemcpyHostToDevice, c->stream));
             m.errorRates = c->d_errorRates;
@@ -735,7 +710,7 @@ extern "C" int maple_set_model(maple_ctx *c, const double *Q16, const double *si
             double e = errorRates ? errorRates[i] : errorRateGlobal;
             acc[i + 1] = acc[i] + log(m.rootFreqs[c->refIdx[i]] * (1.0 - 1.33333 * e) + 0.333333 * e);
         }
-        if (!c->d_rflec) HIPCK(c, hipMalloc((void **)&c->d_rflec, (lRef + 1) * sizeof(double)));
+        HIPCK(c, c->d_rflec.reserve_exact(lRef + 1));
         HIPCK(c, hipMemcpy(c->d_rflec, acc.data(), (lRef + 1) * sizeof(double), hipMemcpyHostToDevice));
         m.rootFreqsLogErrorCumulative = c->d_rflec;
     }
@@ -994,11 +969,7 @@ extern "C" int maple_arena_compact(maple_ctx *c, int64_t nLive, const int32_t *l
     c->tree_set = false; c->tree_stale = false; c->nodes_current = false; c->scan_valid = false; c->cand_root_end = -1;
     c->cand_root_mark = c->cand_root_top = -1;                          // (the lists were renumbered)
     if (c->place) { c->place->valid = false; c->place->rootVect = -1; }
-    for (auto &cs : c->candsets) {
-        if (cs.lists) (void)hipFree(cs.lists);
-        if (cs.frame) (void)hipFree(cs.frame);
-        cs = maple_ctx::CandSet{};
-    }
+    for (auto &cs : c->candsets) cs = maple_ctx::CandSet{};
     return MAPLE_OK;
 }
 
@@ -1119,7 +1090,7 @@ static void lists_update_mark_rows(maple_ctx *c, int32_t n, const int32_t *ids)
     std::vector<int32_t> s(ids, ids + n);
     std::sort(s.begin(), s.end());
     auto has = [&](int32_t id) { return id >= 0 && std::binary_search(s.begin(), s.end(), id); };
-    PlaceAhead *const ah = (c->ahead && c->ahead->active) ? c->ahead : nullptr;
+    PlaceAhead *const ah = (c->ahead && c->ahead->active) ? c->ahead.get() : nullptr;
     const int32_t root = c->dtree.root;
     if (root >= 0 && (size_t)root < c->h_tree_lower.size() && has(c->h_tree_lower[root])) {
         M.rootVect = -1;
@@ -1315,12 +1286,12 @@ extern "C" int maple_candset_create(maple_ctx *c, int32_t n, const int32_t *list
         if (frameIdx[i] < 0 || frameIdx[i] >= nFrames) return fail(c, MAPLE_ERR_ARG, "frameIdx[%d] out of range", i);
     maple_ctx::CandSet cs;
     cs.n = n; cs.nFrames = nFrames;
-    HIPCK(c, hipMalloc((void **)&cs.lists, n * sizeof(int32_t)));
-    HIPCK(c, hipMalloc((void **)&cs.frame, n * sizeof(int32_t)));
+    HIPCK(c, cs.lists.reserve_exact(n));
+    HIPCK(c, cs.frame.reserve_exact(n));
     HIPCK(c, hipMemcpy(cs.lists, lists, n * sizeof(int32_t), hipMemcpyHostToDevice));
     HIPCK(c, hipMemcpy(cs.frame, frameIdx, n * sizeof(int32_t), hipMemcpyHostToDevice));
     *setId = (int32_t)c->candsets.size();
-    c->candsets.push_back(cs);
+    c->candsets.push_back(std::move(cs));
     return MAPLE_OK;
 }
 
@@ -1329,9 +1300,7 @@ extern "C" int maple_candset_destroy(maple_ctx *c, int32_t setId)
     if (!c || setId < 0 || setId >= (int32_t)c->candsets.size()) return MAPLE_ERR_ARG;
     HIPCK(c, hipSetDevice(c->device));
     auto &cs = c->candsets[setId];
-    if (cs.lists) (void)hipFree(cs.lists);
-    if (cs.frame) (void)hipFree(cs.frame);
-    cs.lists = cs.frame = nullptr;
+    cs.lists.release(); cs.frame.release();
     cs.n = 0;
     return MAPLE_OK;
 }
@@ -1574,11 +1543,11 @@ int maple_internal_ev_pair(maple_ctx *c, hipEvent_t *a, hipEvent_t *b, int kind,
     if (c->ev_kind.size() <= slot) { c->ev_kind.resize(slot + 1); c->ev_units.resize(slot + 1); c->ev_bytes.resize(slot + 1); }
     c->ev_kind[slot] = kind; c->ev_units[slot] = units; c->ev_bytes[slot] = bytes;
     if (c->ev_used + 2 > c->evs.size()) {
-        hipEvent_t e0, e1;
-        HIPCK(c, hipEventCreate(&e0));
-        HIPCK(c, hipEventCreate(&e1));
-        c->evs.push_back(e0);
-        c->evs.push_back(e1);
+        Event e0, e1;
+        HIPCK(c, e0.create());
+        HIPCK(c, e1.create());
+        c->evs.push_back(std::move(e0));
+        c->evs.push_back(std::move(e1));
     }
     *a = c->evs[c->ev_used];
     *b = c->evs[c->ev_used + 1];

@@ -73,7 +73,7 @@ int launch_place_score(maple_ctx *c, int nQ, int nF, const int32_t *qFrameLists,
 {
     const long long tiles = (long long)nQ * ((nC + 63) / 64);
     if (tiles > 0x7fffffffLL - (1 << 20)) return fail(c, MAPLE_ERR_ARG, "nQ x nC too large for one launch");
-    if (!c->d_tile_counters) HIPCK(c, hipMalloc((void **)&c->d_tile_counters, 64 * sizeof(int32_t)));
+    HIPCK(c, c->d_tile_counters.reserve_exact(64));
     int32_t *counter = c->d_tile_counters + (c->tile_counter_next++ & 63);
     HIPCK(c, hipMemsetAsync(counter, 0, sizeof(int32_t), c->stream));
     const long long waves = (tiles + 3) / 4;
@@ -421,11 +421,11 @@ static void ahead_spec_body(maple_ctx *c, PlaceParams P, double bLen, int onlyId
     S.status = -100;
     if (hipSetDevice(c->device) != hipSuccess) return;
     const size_t n = S.cols.size(), nl = S.leafCols.size();
-    uint8_t *const hPatchM = (uint8_t *)(A.hSpecPatch + n), *const dPatchM = (uint8_t *)(A.dSpecPatch + n);
+    uint8_t *const hPatchM = (uint8_t *)(A.hSpecPatch + n), *const dPatchM = (uint8_t *)(A.hSpecPatch.dev + n);
     if (n) {
         if (hipMemcpyAsync(A.dSpecLists.p, S.lists.data(), n * sizeof(int32_t), hipMemcpyHostToDevice, A.specStream) != hipSuccess) return;
         const int grid = (int)std::min<size_t>(1024, (n + MAPLE_BLOCK - 1) / MAPLE_BLOCK);
-#define SPEC_COLS(RV, U, SS) k_ahead_cols<RV, U, SS><<<grid, MAPLE_BLOCK, 0, A.specStream>>>(c->d_model, view(c), A.dQ.p + S.row, (int)n, A.dSpecLists.p, bLen, A.dSpecPatch)
+#define SPEC_COLS(RV, U, SS) k_ahead_cols<RV, U, SS><<<grid, MAPLE_BLOCK, 0, A.specStream>>>(c->d_model, view(c), A.dQ.p + S.row, (int)n, A.dSpecLists.p, bLen, A.hSpecPatch.dev)
         if (!rv_ && !u_) SPEC_COLS(false, false, false);
         else if (rv_ && !u_) SPEC_COLS(true, false, false);
         else if (!rv_ && u_ && !ss_) SPEC_COLS(false, true, false);
@@ -536,19 +536,15 @@ static int ahead_refresh(maple_ctx *c, const double **rowOut, bool rowIsCurrent 
     for (size_t i = 0; i < lists.size(); i++) lists[i] = M.h_candList[cols[i]];
     if (A.rootDirty) { cols.push_back((int32_t)(A.ld - 1)); lists.push_back(M.rootVect); }   // (the root's list changed: its new root vector)
     const size_t n = cols.size(), nl = A.dirtyLeaves.size();
-    if (n * sizeof(double) + nl + 64 > A.capPatch) {
-        if (A.hPatch) (void)hipHostFree(A.hPatch);
-        A.hPatch = nullptr; A.capPatch = 0;
-        const size_t want = 2 * (n * sizeof(double) + nl) + (1 << 16);
-        HIPCK(c, hipHostMalloc((void **)&A.hPatch, want, hipHostMallocDefault));
-        void *dp = nullptr;
-        HIPCK(c, hipHostGetDevicePointer(&dp, A.hPatch, 0));
-        A.dPatch = (double *)dp; A.capPatch = want;
+    if (n * sizeof(double) + nl + 64 > A.hPatch.cap || !A.hPatch.dev) {
+        A.hPatch.release();
+        HIPCK(c, A.hPatch.reserve_exact(2 * (n * sizeof(double) + nl) + (1 << 16)));
+        HIPCK(c, A.hPatch.map());
     }
-    uint8_t *const hPatchM = (uint8_t *)(A.hPatch + n), *const dPatchM = (uint8_t *)(A.dPatch + n);
+    uint8_t *const hPatchM = (uint8_t *)(A.hPatch + n), *const dPatchM = (uint8_t *)(A.hPatch.dev + n);
     if (n) {
         TRY(h2d(c, A.dLists, lists.data(), n));
-        TRY(launch_append_queries(c, c->stream, 1, A.dQ.p + A.next, (int)n, A.dLists.p, 1, A.pp.oneMutBLen, A.dPatch, (long long)n, nullptr,
+        TRY(launch_append_queries(c, c->stream, 1, A.dQ.p + A.next, (int)n, A.dLists.p, 1, A.pp.oneMutBLen, A.hPatch.dev, (long long)n, nullptr,
                                   nullptr, nullptr, MAPLE_K_PLACE_SCORE, 0.0));
         A.refreshes++; A.refreshedPairs += (long long)n;
     }
@@ -656,7 +652,7 @@ extern "C" int maple_placement_ahead(maple_ctx *c, int32_t nQ, const int32_t *qL
     TRY(maple_placement_prepare(c, pp));                                 // (tables of the current tree, the root vector)
     PlaceMeta &M = *c->place;
     if (M.nF != 1) return MAPLE_OK;                                      // (reference frames: the single-query path as it is; nTaken = 0)
-    if (!c->ahead) c->ahead = new PlaceAhead();
+    if (!c->ahead) c->ahead.reset(new PlaceAhead());
     PlaceAhead &A = *c->ahead;
     const int32_t nC = (int32_t)M.cand.size(), nCols = nC + 1, nL = (int32_t)M.leaves.size();
     // rows: what fits in a quarter of the free device memory (1 000 000 tips: 2 M columns, 16 MB per row -- 512 rows are 8.4 GB)
@@ -673,32 +669,23 @@ extern "C" int maple_placement_ahead(maple_ctx *c, int32_t nQ, const int32_t *qL
     // (with room: the columns grow by ~2 per placement, and a table that grows by a sliver per batch would be 5 GB freed and
     // allocated again every 512 samples)
     if ((size_t)K * (size_t)A.ld > A.dTable.cap) HIPCK(c, A.dTable.reserve_exact((size_t)K * ((size_t)A.ld + (size_t)A.ld / 8 + 65536)));
-    if ((size_t)A.ld > A.capRow) {
-        for (double *&r : A.hRow) { if (r) (void)hipHostFree(r); r = nullptr; }
-        A.capRow = 0;
+    if ((size_t)A.ld * sizeof(double) > A.hRow[2].cap) {                   // (the last of the three: sized only when all are)
+        for (auto &r : A.hRow) r.release();
         const size_t want = (size_t)A.ld + (size_t)A.ld / 8 + 4096;
-        for (double *&r : A.hRow) HIPCK(c, hipHostMalloc((void **)&r, want * sizeof(double), hipHostMallocDefault));
-        A.capRow = want;
+        for (auto &r : A.hRow) HIPCK(c, r.reserve_exact(want * sizeof(double)));
     }
     const size_t needM = (size_t)K * (size_t)A.ldL;
-    if (needM > A.capMinor) {
-        if (A.hMinor) (void)hipHostFree(A.hMinor);
-        A.hMinor = nullptr; A.capMinor = 0;
-        HIPCK(c, hipHostMalloc(&A.hMinor, needM + needM / 8, hipHostMallocDefault));
-        A.capMinor = needM + needM / 8;
+    if (needM > A.hMinor.cap) {
+        A.hMinor.release();
+        HIPCK(c, A.hMinor.reserve_exact(needM + needM / 8));
     }
-    void *dp = nullptr;
-    if (hipHostGetDevicePointer(&dp, A.hMinor, 0) != hipSuccess || !dp) { (void)hipGetLastError(); return MAPLE_OK; }   // (no zero copy: no rows ahead)
-    A.dMinor = (uint8_t *)dp;
-    if (!A.copyStream) HIPCK(c, hipStreamCreateWithFlags(&A.copyStream, hipStreamNonBlocking));
+    if (A.hMinor.map() != hipSuccess || !A.hMinor.dev) { (void)hipGetLastError(); return MAPLE_OK; }   // (no zero copy: no rows ahead)
+    HIPCK(c, A.copyStream.create());
     if (!A.specStream) {
-        HIPCK(c, hipStreamCreateWithFlags(&A.specStream, hipStreamNonBlocking));
+        HIPCK(c, A.specStream.create());
         HIPCK(c, A.dSpecLists.reserve_exact(MAPLE_SPEC_CAP)); HIPCK(c, A.dSpecLeaf.reserve_exact(MAPLE_SPEC_CAP));
-        A.capSpecPatch = (size_t)MAPLE_SPEC_CAP * (sizeof(double) + 1) + 64;
-        HIPCK(c, hipHostMalloc((void **)&A.hSpecPatch, A.capSpecPatch, hipHostMallocDefault));
-        void *dps = nullptr;
-        HIPCK(c, hipHostGetDevicePointer(&dps, A.hSpecPatch, 0));
-        A.dSpecPatch = (double *)dps;
+        HIPCK(c, A.hSpecPatch.reserve_exact((size_t)MAPLE_SPEC_CAP * (sizeof(double) + 1) + 64));
+        HIPCK(c, A.hSpecPatch.map());
     }
     A.K = K; A.next = 0; A.pp = *pp;
     A.rowInBuf[0] = A.rowInBuf[1] = A.rowInBuf[2] = -1;
@@ -726,7 +713,7 @@ extern "C" int maple_placement_ahead(maple_ctx *c, int32_t nQ, const int32_t *qL
     if (nL > 0) {
         hipLaunchKernelGGL(k_place_minor, dim3(grid_for((int)std::min<long long>((long long)K * nL, 1 << 30))), dim3(MAPLE_BLOCK), 0,
                            c->stream, c->lRef, view(c), K, 1, A.dQ.p, nL, M.d_leafList.p, (const int32_t *)nullptr,
-                           pp->onlyFindIdentical, A.dMinor, (long long)A.ldL, (const int32_t *)nullptr);
+                           pp->onlyFindIdentical, A.hMinor.dev, (long long)A.ldL, (const int32_t *)nullptr);
         HIPCK(c, hipGetLastError());
     }
     HIPCK(c, hipStreamSynchronize(c->stream));
@@ -877,7 +864,7 @@ static int placement_search_impl(maple_ctx *c, int32_t nQ, const int32_t *qLists
         PlaceAhead *const ah = (c->ahead && c->ahead->active && !sup && nQ == 1 && nF == 1 && c->ahead->next < c->ahead->K
                                 && c->ahead->q[c->ahead->next] == qLists[0]
                                 && memcmp(&c->ahead->pp, pp, sizeof(maple_placement_params)) == 0
-                                && (int64_t)nCols < c->ahead->ld - 1 && (int64_t)nL <= c->ahead->ldL) ? c->ahead : nullptr;
+                                && (int64_t)nCols < c->ahead->ld - 1 && (int64_t)nL <= c->ahead->ldL) ? c->ahead.get() : nullptr;
         const double *aheadRow = nullptr;
         const bool specUse = ah && ahead_spec_usable(c);                   // (the traversal was made while the sample before was being placed)
         if (ah) TRY(ahead_refresh(c, &aheadRow, specUse));

@@ -450,7 +450,7 @@ extern "C" int maple_tree_upload(maple_ctx *c, int32_t n, int32_t root, const in
     c->h_tree_totUp.assign(totUp, totUp + n);
     c->h_tree_upRight.assign(upRight, upRight + n);
     c->h_tree_upLeft.assign(upLeft, upLeft + n);
-    if (!c->place) c->place = new PlaceMeta();
+    if (!c->place) c->place.reset(new PlaceMeta());
     c->place->valid = false;
     c->place->rootVect = -1;
     c->dtree.n = n; c->dtree.root = root;
@@ -746,7 +746,7 @@ extern "C" int maple_tree_patch(maple_ctx *c, int32_t nTotal, int32_t nTouched, 
     };
     // (score rows made ahead, maple_placement_ahead: the columns whose list changes here, and the new ones, are scored again for
     // the samples still waiting before the next of them is searched)
-    PlaceAhead *const ah = (c->ahead && c->ahead->active) ? c->ahead : nullptr;
+    PlaceAhead *const ah = (c->ahead && c->ahead->active) ? c->ahead.get() : nullptr;
     if (ah && ah->spec.row == ah->next)                                   // (what the traversal made ahead for the next sample must not have visited)
         for (int i = 0; i < nTouched; i++) { ah->spec.touched.push_back(nodes[i]); if (nodes[i] == root) ah->spec.rootTouched = true; }
     auto dirty_col = [&](int col) { if (ah) { if ((int64_t)col >= ah->ld - 1) ah->active = false; else ah->dirtyCols.push_back(col); } };
@@ -1405,9 +1405,9 @@ extern "C" int maple_spr_search_batch(maple_ctx *c, int32_t n, const int32_t *no
             HIPCK(c, c->s_cache.reserve_exact((size_t)(mZ + preSpare) * nTpre));
             TRY(fin_reserve((size_t)mZ + preSpare));
             if (!c->stream2) {
-                HIPCK(c, hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking));
-                HIPCK(c, hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
-                HIPCK(c, hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
+                HIPCK(c, c->stream2.create());
+                HIPCK(c, c->ev_fork.create(hipEventDisableTiming));
+                HIPCK(c, c->ev_join.create(hipEventDisableTiming));
             }
             std::vector<int32_t> ql(mZ);
             std::vector<uint8_t> qt(mZ);

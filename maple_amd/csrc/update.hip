@@ -107,7 +107,7 @@ __global__ __launch_bounds__(64) void k_update_items_wave(MAPLE_UPDATE_ITEM_ARGS
 
 namespace {
 
-struct UpdateScratch {                 // per-context, persistent: flags per node, cleared through the touched list
+struct UpdateScratch : ScratchBase {              // per-context, persistent: flags per node, cleared through the touched list
     std::vector<uint8_t> dLow, dUp, dDist, dCh0, dCh1, inFrontier, inTodo;
     std::vector<int32_t> touched;
     std::vector<int32_t> replacedNodes;   // nodes one of whose four lists (or whose branch length) the last call replaced
@@ -131,14 +131,8 @@ struct UpdateScratch {                 // per-context, persistent: flags per nod
 
 static UpdateScratch &update_scratch(maple_ctx *c)
 {
-    if (!c->upd) c->upd = new UpdateScratch();
-    return *(UpdateScratch *)c->upd;
-}
-
-void update_scratch_free(maple_ctx *c)
-{
-    delete (UpdateScratch *)c->upd;
-    c->upd = nullptr;
+    if (!c->upd) c->upd.reset(new UpdateScratch());
+    return *static_cast<UpdateScratch *>(c->upd.get());
 }
 
 // lists[i] passed through the branch above nodes[i] (up or down) where that branch carries mutations, M:3749-3877

@@ -6,4 +6,3 @@ __attribute__((visibility("hidden")))
 int witness_score(maple_ctx *c, hipStream_t st, int nQ, const int32_t *qList, const uint8_t *qTip, const double *qBLen, int nC,
                   const int32_t *cand, const int32_t *outCol, double *out, long long ldOut, unsigned long long *finMask, int nWords,
                   double meanCandBytes, double queryBytes, long long *pairsOut);
-__attribute__((visibility("hidden"))) void witness_scratch_free(maple_ctx *c);

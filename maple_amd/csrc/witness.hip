@@ -26,7 +26,7 @@ namespace {
 
 #define WIT_BLOCK 256
 
-struct WitnessScratch {
+struct WitnessScratch : ScratchBase {
     DevBuf<int32_t> hist, witB, cnt, start, cursor, bcand, qCnt, pairQ, pairK;
     DevBuf<long long> qOff;
 };
@@ -168,16 +168,6 @@ void k_wit_score(const DevModel *__restrict__ mp, ArenaView av, long long nPairs
 
 }  // namespace
 
-void witness_scratch_free(maple_ctx *c)
-{
-    WitnessScratch *W = (WitnessScratch *)c->witness;
-    if (!W) return;
-    W->hist.release(); W->witB.release(); W->cnt.release(); W->start.release(); W->cursor.release(); W->bcand.release();
-    W->qCnt.release(); W->pairQ.release(); W->pairK.release(); W->qOff.release();
-    delete W;
-    c->witness = nullptr;
-}
-
 // Rows of the score table for nQ whole-tree searches (removed lists qList, ALL searched with removedBLen = 0 -- the caller checks
 // its host copy of the lengths -- no error model; on a tree with local references both sides re-expressed in the root's frame) against the nC candidate lists `cand`: out[q * ldOut + outCol[k]] for the finite scores,
 // finMask[q * nWords + k / 64] bit k % 64 set exactly for those.  Blocks on `st` once (the number of pairs).
@@ -186,8 +176,8 @@ int witness_score(maple_ctx *c, hipStream_t st, int nQ, const int32_t *qList, co
                   double meanCandBytes, double queryBytes, long long *pairsOut)
 {
     if (c->dm.usingErrorRate) return fail(c, MAPLE_ERR_STATE, "witness_score: not valid with an error model");
-    if (!c->witness) c->witness = new WitnessScratch();
-    WitnessScratch &W = *(WitnessScratch *)c->witness;
+    if (!c->witness) c->witness.reset(new WitnessScratch());
+    WitnessScratch &W = *static_cast<WitnessScratch *>(c->witness.get());
     const int nB = 4 * (c->lRef + 1) + 1;                                   // bucket 0 = no witness, 1 + site * 4 + nucleotide
     HIPCK(c, W.hist.reserve((size_t)nB)); HIPCK(c, W.cnt.reserve((size_t)nB)); HIPCK(c, W.cursor.reserve((size_t)nB));
     HIPCK(c, W.start.reserve((size_t)nB + 1));

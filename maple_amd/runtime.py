@@ -32,7 +32,7 @@ EXPORTS = [
 # include/maple_hip_debug.h: measurement aids and test hooks, exported by libmaple_hip_debug.so only (Device(..., debug=True))
 DEBUG_EXPORTS = ["maple_debug_wave_append_batch", "maple_debug_trace_query", "maple_debug_trace_read", "maple_debug_calib_walk",
                  "maple_debug_calib_write", "maple_debug_gpv_batch", "maple_debug_simplify_batch", "maple_debug_frontier_levels",
-                 "maple_debug_frontier_pass_batch"]
+                 "maple_debug_frontier_pass_batch", "maple_debug_live_resources"]
 LIB_PATH_DEBUG = os.path.join(HERE, "libmaple_hip_debug.so")
 
 
@@ -119,6 +119,16 @@ def _u8(x):
 
 def _f64(x):
     return np.ascontiguousarray(x, dtype=np.float64)
+
+
+def debug_live_resources():
+    """(allocations, bytes, handles) the library holds at this moment in this process, over all contexts: device and page-locked
+    allocations with their bytes, streams and events (maple_debug_live_resources, debug library).  Compare differences."""
+    a, b, h = C.c_int64(), C.c_int64(), C.c_int64()
+    rc = load_library(debug=True).maple_debug_live_resources(C.byref(a), C.byref(b), C.byref(h))
+    if rc != 0:
+        raise MapleError(f"maple_debug_live_resources failed ({rc})", rc)
+    return a.value, b.value, h.value
 
 
 class Device:

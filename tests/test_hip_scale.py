@@ -29,7 +29,7 @@ def world_model_kwargs(mode, l_ref, seed=2):
     return kw
 
 
-def build(n_tips, mode, seed=2):
+def build(n_tips, mode, seed=2, **dev_kw):
     from maple_amd.host import reference_tables, tip_genome_list
     from maple_amd.runtime import Device
     from maple_amd.synth import make_dataset
@@ -39,7 +39,7 @@ def build(n_tips, mode, seed=2):
                         frac_with_n=0.05, frac_ambig=0.05)
     ref_idx, rf = reference_tables(data.ref)
     kw = world_model_kwargs(mode, len(ref_idx), seed)
-    dev = Device(ref_idx, rf, arena_bytes=3 << 30)
+    dev = Device(ref_idx, rf, **dict(dict(arena_bytes=3 << 30), **dev_kw))
     dev.set_model(**kw)
     orc = Oracle(ref_idx, rf)
     orc.set_model(**kw)
@@ -1344,12 +1344,12 @@ def check_against_oracle(checks, min_checks):
     return ties
 
 
-def small_world(mode, n_tips, seed, n_add, near_root=0):
+def small_world(mode, n_tips, seed, n_add, near_root=0, **dev_kw):
     """A small tree (n_tips tips) and n_add new samples: perturbed copies of random tips, every 25th an exact copy (a minor
-    sequence), and -- near_root > 0 -- copies of the near_root tips closest to the root."""
+    sequence), and -- near_root > 0 -- copies of the near_root tips closest to the root.  dev_kw: for the Device."""
     from maple_amd.host import tip_genome_list
     from maple_amd.synth import perturb_diffs
-    data, dev, orc, m = build(n_tips, mode, seed=seed)
+    data, dev, orc, m = build(n_tips, mode, seed=seed, **dev_kw)
     kw = world_model_kwargs(mode, dev.lRef, seed)
     tip_kw = dict(error_rates=kw["errorRates"]) if mode == "siteerr" else {}
     prng = np.random.default_rng(seed + 7)
@@ -1546,9 +1546,10 @@ def test_announced_loop_interleaved_calls_mid_batch():
 
 def test_announced_loop_closed_mid_batch_then_a_fresh_context():
     """A context closed halfway through an announced batch, with the traversal of the next sample made ahead on (its thread is
-    joined before anything is freed); a fresh context then runs the whole loop: the plain loop's results."""
-    from maple_amd.runtime import Device
-    data, dev, orc, m, new_lists = small_world("ratevar", 300, 43, 48)
+    joined before anything is freed); a fresh context then runs the whole loop: the plain loop's results.  The context closed
+    mid-batch leaves no GPU resource behind (live_resources)."""
+    before = live_resources()
+    data, dev, orc, m, new_lists = small_world("ratevar", 300, 43, 48, debug=True)
     pkw = small_pkw(dev.lRef)
     mark = dev.mark()
     plain = serial_loop(dev, m, new_lists, pkw, ahead=0)
@@ -1557,9 +1558,138 @@ def test_announced_loop_closed_mid_batch_then_a_fresh_context():
     assert half["results"] == plain["results"][:24]
     assert dev.placement_ahead_stats()["traversals_ahead_used"] > 0
     dev.close()
+    assert np.array_equal(live_resources(), before), (live_resources(), before)
     data2, dev2, orc2, m2, lists2 = small_world("ratevar", 300, 43, 48)
     assert all(a == b for a, b in zip(lists2, new_lists))
     whole = serial_loop(dev2, m2, lists2, pkw, ahead=48)
     assert whole["results"] == plain["results"]
     assert dev2.placement_ahead_stats()["searches"] == len(new_lists)
     dev2.close()
+
+
+# ---- a closed context leaves nothing behind ------------------------------------------------------------------------------
+# Every GPU resource of a context -- device and page-locked memory, streams, events -- belongs to an owning member that counts
+# itself into a process-wide ledger (maple_debug_live_resources: allocations, bytes, handles).  Each test reads the ledger before
+# its context is created and after close() and requires the three differences to be zero (differences: the counters are shared
+# by every context of the process).
+
+def live_resources():
+    from maple_amd.runtime import debug_live_resources
+    return np.asarray(debug_live_resources(), dtype=np.int64)
+
+
+def tiny_context(**kw):
+    from maple_amd.runtime import Device
+    ref_idx = np.arange(2000, dtype=np.uint8) % 4
+    return Device(ref_idx, [0.25, 0.25, 0.25, 0.25], debug=True, **kw)
+
+
+def test_live_resources_bare_context():
+    before = live_resources()
+    dev = tiny_context(arena_bytes=64 << 20)
+    dev.close()
+    assert np.array_equal(live_resources(), before), (live_resources(), before)
+
+
+def test_live_resources_move_with_a_context():
+    """The ledger is wired to the owners: a context alone holds its arena, its tables and its stream."""
+    before = live_resources()
+    dev = tiny_context(arena_bytes=64 << 20)
+    held = live_resources() - before
+    dev.close()
+    assert held[0] >= 12 and held[1] >= 64 << 20 and held[2] >= 1, held
+    assert np.array_equal(live_resources(), before), (live_resources(), before)
+
+
+def test_live_resources_two_contexts_closed_in_reverse_order():
+    before = live_resources()
+    a = tiny_context(arena_bytes=64 << 20)
+    b = tiny_context(arena_bytes=32 << 20)
+    a.set_model(Q)
+    b.set_model(Q, siteRates=np.ones(2000))
+    b.close()
+    a.close()
+    assert np.array_equal(live_resources(), before), (live_resources(), before)
+
+
+def test_live_resources_failed_creation():
+    """maple_create refused for lack of memory (an arena of twice the card's memory: one allocation request the runtime turns
+    down) frees what it had got by then."""
+    import torch
+    from maple_amd.runtime import MapleError
+    total = int(torch.cuda.mem_get_info(0)[1])
+    before = live_resources()
+    with pytest.raises(MapleError):
+        tiny_context(arena_bytes=2 * total)
+    assert np.array_equal(live_resources(), before), (live_resources(), before)
+
+
+def deep_round(dev, m, upload):
+    """One deep SPR round over every node of the tree, frontier tier; the tree uploaded through ``upload``."""
+    import bench
+    upload()
+    return dev.spr_search_batch(bench.preorder_nodes(m), **bench.search_kwargs(dev.lRef))
+
+
+def test_live_resources_after_every_kind_of_call():
+    """A 300-tip world with site-specific error rates (the error-rate tables exist) that has been through pair batches, an
+    announced placement loop with updatePartials and tree patches, a traced search, a deep SPR round and a candidate set it
+    never destroyed."""
+    import bench
+    before = live_resources()
+    data, dev, orc, m, new_lists = small_world("siteerr", 300, 47, 8, debug=True, arena_bytes=1 << 30)
+    assert (live_resources() - before > 0).all()
+
+    def upload():
+        dev.upload_tree(m.root, m.parent, m.children[:, 0], m.children[:, 1], m.dist, m.is_tip, m.lower, m.up_right, m.up_left,
+                        m.tot_up, -np.ones(m.n_nodes, dtype=np.int32))
+    tips = np.nonzero(m.is_tip)[0][:64]
+    a, b = m.lower[tips], m.lower[tips[::-1]]
+    merged = dev.merge_batch(a, 1e-4, True, b, 2e-4, True, False)
+    ok = merged >= 0
+    assert ok.any()
+    assert np.isfinite(dev.append_batch(merged[ok], a[ok], True, 1.0 / dev.lRef)).any()
+    dev.blen_batch(merged[ok], a[ok], True)
+    nodes = bench.preorder_nodes(m)
+    upload()
+    dev.debug_trace_query(0)
+    dev.spr_search_batch(nodes[:32], **bench.search_kwargs(dev.lRef))
+    assert len(dev.debug_trace_read()[0]) > 0
+    dev.debug_trace_query(-1)
+    g = deep_round(dev, m, upload)
+    assert (g["status"] == 0).sum() > 100
+    dev.candset_create(m.tot_up[m.candidate_nodes(0.0)], np.zeros(len(m.candidate_nodes(0.0)), dtype=np.int32), 1)
+    loop = serial_loop(dev, m, new_lists, small_pkw(dev.lRef), ahead=8)   # (placement, rows made ahead, update_partials, tree_patch)
+    assert sum(r[0] == 0 for r in loop["results"]) > 0 and len(dev.update_partials_touched()) > 0
+    dev.close()
+    assert np.array_equal(live_resources(), before), (live_resources(), before)
+
+
+def test_live_resources_after_whole_tree_searches_on_a_tree_with_local_references():
+    """The same on a 300-tip tree with rate variation that carries MAT local references: a search from a zero-length branch
+    runs over its budget and becomes a whole-tree search, whose removed list goes into every reference frame on the device
+    (fan_out_level) before the dense kernel scores it -- scratch of its own, and dense launches in the timing records."""
+    import bench
+    from maple_amd.mat import add_local_references
+    from maple_amd.tree_host import HostTree
+    before = live_resources()
+    data, dev, orc, m = build(300, "ratevar", seed=4, debug=True, arena_bytes=1 << 30)
+    ht = HostTree.from_mirror(m)
+    assert add_local_references(dev, ht, 50) > 0
+    dist = np.asarray([float(x or 0.0) for x in ht.dist])
+    nodes = bench.preorder_nodes(m)
+    assert (dist[nodes] == 0.0).any()
+
+    def upload():
+        dev.upload_tree(ht.root, m.parent, m.children[:, 0], m.children[:, 1], dist, m.is_tip, ht.id_lower, ht.id_upRight, ht.id_upLeft,
+                        ht.id_totUp, ht.id_mut)
+    dev.timing_reset()
+    g = deep_round(dev, m, upload)
+    assert (g["status"] == 0).sum() > 100
+    dense = dev.timing_read_kind(dev.KIND_SPR_SCORE)
+    assert dense[0] > 0 and dense[2] > 0, dense                             # (whole-tree searches were scored: launches, searches)
+    dev.debug_trace_query(0)
+    dev.spr_search_batch(nodes[:32], **bench.search_kwargs(dev.lRef))
+    dev.debug_trace_query(-1)
+    dev.close()
+    assert np.array_equal(live_resources(), before), (live_resources(), before)
