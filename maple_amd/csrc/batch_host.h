@@ -45,9 +45,10 @@ static int check_ids(maple_ctx *c, int32_t n, const int32_t *ids, bool allowNeg,
     return MAPLE_OK;
 }
 
-static inline int ev_pair(maple_ctx *c, hipEvent_t *a, hipEvent_t *b, int kind = 0, double units = 0.0, double bytes = 0.0)
+static inline int ev_pair(maple_ctx *c, hipEvent_t *a, hipEvent_t *b, int kind = 0, double units = 0.0, double bytes = 0.0,
+                          size_t *slot = nullptr)
 {
-    return maple_internal_ev_pair(c, a, b, kind, units, bytes);
+    return maple_internal_ev_pair(c, a, b, kind, units, bytes, slot);
 }
 
 template <class T> static int h2d(maple_ctx *c, DevBuf<T> &b, const T *src, size_t n)

@@ -414,6 +414,6 @@ static inline int wave_item_max(const maple_ctx *c, int dflt)
     } while (0)
 
 // one (start, stop) pair of HIP events from the context's pool, tagged with the kind of launch it brackets and the work it
-// did (maple_timing_read_kind); defined in maple_hip.hip
+// did (maple_timing_read_kind); *slot (optional): the pair's timing record, ev_kind / ev_units / ev_bytes[*slot]; defined in maple_hip.hip
 __attribute__((visibility("hidden")))
-int maple_internal_ev_pair(maple_ctx *c, hipEvent_t *a, hipEvent_t *b, int kind, double units, double bytes);
+int maple_internal_ev_pair(maple_ctx *c, hipEvent_t *a, hipEvent_t *b, int kind, double units, double bytes, size_t *slot = nullptr);

@@ -30,10 +30,12 @@
 // items are whole-tree searches and go to the dense tier (status -5), as before.
 #include "ctx_host.h"
 #include "frontier_dev.h"
+#include "search_plan.h"
 
 #include <chrono>
 
 using namespace frt;
+namespace plan = maple::plan;
 
 namespace {
 
@@ -1110,11 +1112,28 @@ struct FrontierScratch : ScratchBase {
     std::vector<unsigned long long> lastLvl;        // [levels][4]: the level ranges of the last call (frontier_level_profile)
     std::vector<size_t> lastSlotsU, lastSlotsC;    // ... and the timing slots of its level kernels
     long long lastU = -1, lastC = -1, lastR = 0;     // items of the last call (for frontier_export), -1: none
-    long long needR = 0;
-    long long needU = 0, needC = 0, needL = 0, needW = 0, needA = 0, needM = 0;   // what the last call asked of the pools, and its searches
-    bool lastOverflow = false;         // ... and whether one of them ran over
+    plan::FrontierNeeds need;                        // what the last call that counts asked of the pools (plan::remember_frontier)
     FPools lastPools{};
     int capE = 0;                                    // entries of a per-lane scratch slab
+    plan::FrontierCaps caps() const                  // what the buffers hold, for plan::plan_frontier / bind_frontier
+    {
+        plan::FrontierCaps k;
+        k.itemsU = itemsU.cap; k.itemsC = itemsC.cap; k.tw = tw.cap; k.ta = ta.cap; k.trec = trec.cap; k.tflag = tflag.cap; k.arec = arec.cap;
+        k.sw = sw.cap; k.sa = sa.cap; k.sais = sais.cap; k.bw = bw.cap; k.bw2 = bw2.cap; k.recs = recs.cap;
+        k.perm = perm.cap; k.perm2 = perm2.cap; k.perm3 = perm3.cap; k.perm4 = perm4.cap; k.visit = visit.cap; k.lsize = lsize.cap;
+        k.lpos = lpos.cap; k.lpar = lpar.cap; k.passList = passList.cap; k.passListR = passListR.cap;
+        return k;
+    }
+};
+
+// An error once the side streams are in use must not return with kernels in flight on any of the three streams -- the caller may
+// reuse or free the pools.  Armed where the side streams are first used; every way out but the successful one (disarm) awaits
+// them, so the launches in between are ordinary HIPCK / TRY lines.
+struct QuiesceOnExit {
+    hipStream_t s[3];
+    bool armed = true;
+    ~QuiesceOnExit() { if (armed) for (hipStream_t x : s) (void)hipStreamSynchronize(x); }
+    void disarm() { armed = false; }
 };
 
 }  // namespace
@@ -1131,9 +1150,10 @@ int frontier_search(maple_ctx *c, const SearchParams &P, int m, const int32_t *n
     const auto tEnter = std::chrono::steady_clock::now();
     auto sinceEnter = [&] { return std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - tEnter).count() * 1e-3; };
     const bool dbgTime = c->tuning.verbose != 0;
-    // pools, sized for the batch and bounded by what the device has free
-    size_t freeB = 0, totalB = 0;
-    if (hipMemGetInfo(&freeB, &totalB) != hipSuccess) freeB = (size_t)8 << 30;
+    // pools, sized for the batch and bounded by what the device has free: the arithmetic is plan::plan_frontier (search_plan.h)
+    plan::FrontierPlanIn in;
+    size_t totalB = 0;
+    if (hipMemGetInfo(&in.freeBytes, &totalB) != hipSuccess) in.freeBytes = (size_t)8 << 30;
     const size_t allocs0 = devbuf_stats().allocs, allocBytes0 = devbuf_stats().bytes;
     struct PoolCap { const char *name; const size_t *cap; size_t elem, before; };
     PoolCap poolCaps[] = {{"itemsU", &F.itemsU.cap, 1, 0}, {"itemsC", &F.itemsC.cap, 1, 0}, {"tw", &F.tw.cap, 8, 0}, {"ta", &F.ta.cap, 8, 0},
@@ -1141,141 +1161,81 @@ int frontier_search(maple_ctx *c, const SearchParams &P, int m, const int32_t *n
                           {"bw", &F.bw.cap, 8, 0}, {"bw2", &F.bw2.cap, 8, 0}, {"visit", &F.visit.cap, 1, 0}, {"recs", &F.recs.cap, 1, 0},
                           {"perm", &F.perm.cap, 4, 0}, {"passList", &F.passList.cap, 4, 0}};
     for (PoolCap &pc : poolCaps) pc.before = *pc.cap;
-    const size_t held = F.itemsU.cap + F.itemsC.cap + F.tw.cap * sizeof(uint2) + F.ta.cap * sizeof(double)
-                        + F.sw.cap * sizeof(uint2) + F.sa.cap * sizeof(double) + F.sais.cap * sizeof(double) + F.bw.cap * 48 + F.bw2.cap * 48;
-    const double room = 0.5 * (double)(freeB + held);
-    // (first guesses, for a context's first batch: afterwards the pools go by what the batch before used.  With an error model a fifth
-    // of the searches runs to the budget -- a quarter of it per search on average, and three times the temporary lists: measured 1 500
-    // cached items and 61 lists per search at 1 000 000 tips, where a first call that ran over took 2.9-5.3 s and the two calls
-    // after it 2.3-3.1 s before the pools had grown)
-    const bool longSearches = c->dm.usingErrorRate && !(wide && wide->forceWide);
-    const long long perSearchC = longSearches ? std::min<long long>(budget, std::max<long long>(768, budget / 4)) : std::min<long long>(budget, 768);
-    long long capC = std::max<long long>(1 << 16, std::max((long long)m * perSearchC, itemsHint));
-    long long capU = std::max<long long>(1 << 14, (long long)m * std::min<long long>(budget, 16));
-    // (roots: the cached-regime items the list-updating items push -- the upper part of the cached pool)
-    long long capR = std::max<long long>(1 << 16, std::min(capC, (long long)m * std::min<long long>(budget, 32)));
-    const long long meanEnt = std::max<long long>(16, c->h_n_ent.empty() ? 64 : c->used_ent / (long long)c->h_n_ent.size());   // entries per list in the arena
-    long long capL = (longSearches ? 6 : 2) * capU;
-    long long capW = 2 * capL * meanEnt, capA = capW;
-    if (F.needM > 0 && !(wide && wide->forceWide)) {
-        // what the last batch asked for, scaled to this one: with an error model the searches are several times as long as the
-        // first guess, and a pool that runs over hands its searches back
-        // (after an overflow the asks themselves are too low -- the searches that were handed back stopped asking: twice, not 1.25 x)
-        const double f = (F.lastOverflow ? 2.0 : 1.25) * std::min(16.0, (double)m / (double)F.needM);   // (a far smaller batch is no measure: capped)
-        capU = std::max(capU, (long long)(f * F.needU)); capC = std::max(capC, (long long)(f * F.needC)); capR = std::max(capR, (long long)(f * F.needR));
-        capL = std::max(capL, (long long)(f * F.needL));
-        // (the words' first guess goes with the arena's mean list length, which moves by an entry when the tree is uploaded again:
-        // 47 -> 48 made two 5 GB pools "grow" by half -- 0.73 s of the first round on a changed tree.  Once a batch has said what it
-        // used, that alone sizes them.)
-        capW = std::max<long long>(1 << 20, (long long)(f * F.needW)); capA = std::max<long long>(1 << 20, (long long)(f * F.needA));
-    }
-    // per-lane scratch for lists of up to capE entries (two average lists merged, with room); the few longer ones -- near the
-    // root -- take pieces of a shared region.  As many lanes as the GPU holds at once at this kernel's occupancy.
-    // (in steps of 32 and never below what the slabs were cut for: they are 6 GB, and 282 -> 288 entries would allocate them again)
-    const int capE = std::max(F.capE, std::max(256, std::min(1024, (6 * (int)meanEnt + 31) / 32 * 32)));
-    F.capE = capE;
-    long long scratchLanes = m <= 64 ? 16384 : 256ll * 4 * 4 * 64;         // 256 CUs x 4 SIMDs x 4 wavefronts (a handful of searches: what they can use)
-    // slabs beyond the lanes' own: one per wavefront of the two wavefront-wide kernels (256 + 1 280 <= 2 048) and, on a tree with MAT
-    // local references, one per lane of k_fr_pass (256 workgroups), which runs next to k_fr_updating
-    const bool matTree = c->tree_has_mut;
-    const long long extraSlabs = 2048 + (matTree ? 256ll * FR_BLOCK : 0);
-    while (scratchLanes > 16384 && (double)(scratchLanes + extraSlabs) * capE * 64 > 0.25 * room) scratchLanes /= 2;
-    const int gridUpd = (int)(scratchLanes / FR_BLOCK);
-    const long long capBig = std::max<long long>(1 << 20, 64ll * 1024 * std::max(1, c->tree_max_ent));
-    const long long capBig2 = matTree ? std::max<long long>(1 << 20, capBig / 4) : 0;
-    {   // What a pool already holds it keeps (a request below its capacity costs nothing, and a pool that shrinks and grows from
-        // call to call is freed and allocated again -- tens of GB: 1.3 s of a 1 000 000-tip step); what a pool would GROW by is cut
-        // down proportionally if the total would not fit.  (The temporary lists' pools used to be set back to their first guess
-        // whenever the total met the room -- always, at 1 000 000 tips: the list words overflowed on EVERY step and sent 15 000
-        // of 131 072 searches to the one-lane kernel, 550 ms.)
-        const long long curU = (long long)(F.itemsU.cap / sizeof(FItem)), curCR = (long long)(F.itemsC.cap / sizeof(FItem));
-        const long long curL = (long long)std::min(F.trec.cap, F.tflag.cap);
-        const long long curW = (long long)F.tw.cap, curA = (long long)F.ta.cap;
-        const double perItem = (double)(sizeof(FItem) + sizeof(FVisit) + 12);
-        const double fixed = (double)(scratchLanes + extraSlabs) * capE * 64 + (double)(capBig + capBig2) * 48;
-        const double base = (double)(curCR + curU) * perItem + (double)(curW + curA) * 8 + (double)curL * 24 + fixed;
-        const double gCR = std::max<double>(0.0, (double)(capC + capR - curCR)), gU = std::max<double>(0.0, (double)(capU - curU));
-        const double gL = std::max<double>(0.0, (double)(capL - curL)), gW = std::max<double>(0.0, (double)(capW - curW)), gA = std::max<double>(0.0, (double)(capA - curA));
-        const double growth = (gCR + gU) * perItem + (gW + gA) * 8 + gL * 24;
-        double f = 1.0;
-        if (base + growth > room && growth > 0) f = std::max(0.0, (room - base) / growth);
-        const double wantCR = std::max<double>((double)curCR, (double)curCR + f * gCR);
-        const double shareR = (double)capR / (double)(capC + capR);
-        capR = std::max<long long>(1 << 16, (long long)(wantCR * shareR)); capC = std::max<long long>(1 << 16, (long long)wantCR - capR);
-        capU = std::max<long long>(1 << 14, std::max(curU, (long long)(curU + f * gU)));
-        capL = std::max<long long>(2 * (1 << 14), std::max(curL, (long long)(curL + f * gL)));
-        capW = std::max<long long>(1 << 20, std::max(curW, (long long)(curW + f * gW)));
-        capA = std::max<long long>(1 << 20, std::max(curA, (long long)(curA + f * gA)));
-    }
-    const long long capRecs = std::max<long long>(1 << 14, (long long)m * 16);
-    auto grow = [](size_t want, size_t cap) { return want <= cap ? cap : std::max(want, cap + cap / 2); };
-    HIPCK(c, F.itemsU.reserve_exact(grow((size_t)capU * sizeof(FItem), F.itemsU.cap)));
-    HIPCK(c, F.itemsC.reserve_exact(grow((size_t)(capC + capR) * sizeof(FItem), F.itemsC.cap)));
+    in.m = m; in.budget = budget; in.itemsHint = itemsHint;
+    in.usingErrorRate = c->dm.usingErrorRate; in.forceWide = wide && wide->forceWide; in.matTree = c->tree_has_mut;
+    in.nLists = c->h_n_ent.size(); in.usedEnt = c->used_ent; in.treeMaxEnt = c->tree_max_ent; in.waveAllBelow = c->tuning.waveAllBelow;
+    // (tests/search_plan_main.cpp runs the plans with these sizes, and with 256 / 24 / 176 for the three constants' defaults)
+    static_assert(sizeof(FItem) == 96 && sizeof(FVisit) == 32 && sizeof(FRec) == 48 && FR_BLOCK == 256, "tests/search_plan_main.cpp");
+    in.szItem = sizeof(FItem); in.szVisit = sizeof(FVisit); in.szRec = sizeof(FRec);
+    in.frBlock = FR_BLOCK; in.heavyMult = FR_HEAVY_MULT; in.bigMin = FR_BIG_MIN;
+    in.cap = F.caps(); in.capE = F.capE; in.need = F.need;
+    const plan::FrontierPlan pl = plan::plan_frontier(in);
+    F.capE = pl.capE;
+    HIPCK(c, F.itemsU.reserve_exact(pl.resItemsU));
+    HIPCK(c, F.itemsC.reserve_exact(pl.resItemsC));
     HIPCK(c, F.srch.reserve((size_t)m * sizeof(FSearch)));
-    HIPCK(c, F.recs.reserve_exact(grow((size_t)capRecs * sizeof(FRec), F.recs.cap)));
+    HIPCK(c, F.recs.reserve_exact(pl.resRecs));
     HIPCK(c, F.ctr.reserve(sizeof(FCtr)));
-    HIPCK(c, F.tw.reserve_exact(grow((size_t)capW, F.tw.cap)));
-    HIPCK(c, F.ta.reserve_exact(grow((size_t)capA, F.ta.cap)));
-    HIPCK(c, F.trec.reserve_exact(grow((size_t)capL, F.trec.cap)));
-    HIPCK(c, F.arec.reserve_exact(grow(c->h_n_ent.size(), F.arec.cap)));
-    HIPCK(c, F.tflag.reserve_exact(grow((size_t)capL, F.tflag.cap)));
-    HIPCK(c, F.sw.reserve_exact((size_t)(scratchLanes + extraSlabs) * capE));
-    HIPCK(c, F.sa.reserve_exact((size_t)(scratchLanes + extraSlabs) * capE * 5));
-    HIPCK(c, F.sais.reserve_exact((size_t)(scratchLanes + extraSlabs) * capE * 2));
-    HIPCK(c, F.bw.reserve_exact((size_t)capBig));
-    HIPCK(c, F.ba.reserve_exact((size_t)capBig * 5));
-    if (capBig2) { HIPCK(c, F.bw2.reserve_exact((size_t)capBig2)); HIPCK(c, F.ba2.reserve_exact((size_t)capBig2 * 5)); }
+    HIPCK(c, F.tw.reserve_exact(pl.resTw));
+    HIPCK(c, F.ta.reserve_exact(pl.resTa));
+    HIPCK(c, F.trec.reserve_exact(pl.resTrec));
+    HIPCK(c, F.arec.reserve_exact(pl.resArec));
+    HIPCK(c, F.tflag.reserve_exact(pl.resTflag));
+    HIPCK(c, F.sw.reserve_exact(pl.resSw));
+    HIPCK(c, F.sa.reserve_exact(pl.resSa));
+    HIPCK(c, F.sais.reserve_exact(pl.resSais));
+    HIPCK(c, F.bw.reserve_exact(pl.resBw));
+    HIPCK(c, F.ba.reserve_exact(pl.resBa));
+    HIPCK(c, F.bw2.reserve_exact(pl.resBw2));                             // (0 without local references: nothing is reserved)
+    HIPCK(c, F.ba2.reserve_exact(pl.resBa2));
     HIPCK(c, F.nodes.reserve((size_t)m));
     HIPCK(c, F.out.reserve((size_t)m * sizeof(SearchOut)));
+    // ... and what follows from the capacities the buffers ended up with (one kept from a larger call stays as it is)
+    const plan::FrontierBound bd = plan::bind_frontier(in, pl, F.caps());
     FPools fp;
     fp.U = (FItem *)F.itemsU.p; fp.C = (FItem *)F.itemsC.p;
-    fp.capU = (long long)(F.itemsU.cap / sizeof(FItem)); fp.capC = (long long)(F.itemsC.cap / sizeof(FItem));
-    // (a buffer kept from a larger call: both parts grow with it)
-    fp.capCC = fp.capC - std::max(capR, (long long)((double)fp.capC * capR / (double)(capC + capR)));
+    fp.capU = bd.capU; fp.capC = bd.capC; fp.capCC = bd.capCC;
     fp.tw = F.tw.p; fp.ta = F.ta.p; fp.trec = F.trec.p; fp.arec = F.arec.p; fp.nArec = (int32_t)c->h_n_ent.size();
-    fp.capW = (long long)F.tw.cap; fp.capA = (long long)F.ta.cap;
+    fp.capW = bd.capW; fp.capA = bd.capA;
     fp.tflag = F.tflag.p;
-    fp.capL = (long long)std::min(F.trec.cap, F.tflag.cap);
-    HIPCK(c, F.perm.reserve_exact(std::max(F.perm.cap, (size_t)fp.capU)));
-    HIPCK(c, F.perm2.reserve_exact(std::max(F.perm2.cap, (size_t)fp.capU)));
-    HIPCK(c, F.perm3.reserve_exact(std::max(F.perm3.cap, (size_t)fp.capU)));
-    HIPCK(c, F.perm4.reserve_exact(std::max(F.perm4.cap, (size_t)fp.capU)));
+    fp.capL = bd.capL;
+    HIPCK(c, F.perm.reserve_exact(bd.resPerm));
+    HIPCK(c, F.perm2.reserve_exact(bd.resPerm2));
+    HIPCK(c, F.perm3.reserve_exact(bd.resPerm3));
+    HIPCK(c, F.perm4.reserve_exact(bd.resPerm4));
     fp.perm = F.perm.p; fp.perm2 = F.perm2.p; fp.perm3 = F.perm3.p; fp.perm4 = F.perm4.p;
-    fp.waveAllBelow = c->tuning.waveAllBelow > 0 ? c->tuning.waveAllBelow : (c->tuning.waveAllBelow < 0 ? 0 : 49152);
+    fp.waveAllBelow = pl.waveAllBelow;
     // the visiting-order layout of the items (k_fr_layout_*): one 32-byte record per item, the levels' ranges, per-search bases
     fp.maxLevels = 4096;
-    fp.capVisit = fp.capU + fp.capC;
-    const bool layoutOK = m > 64 && fp.capVisit < (1ll << 31) - 64;       // (ranks are 32-bit; a handful of searches is not worth 90 launches)
-    if (layoutOK) {
-        HIPCK(c, F.visit.reserve_exact(std::max(F.visit.cap, (size_t)fp.capVisit * sizeof(FVisit))));
-        HIPCK(c, F.lsize.reserve_exact(std::max(F.lsize.cap, (size_t)fp.capVisit)));
-        HIPCK(c, F.lpos.reserve_exact(std::max(F.lpos.cap, (size_t)fp.capVisit)));
-        HIPCK(c, F.lpar.reserve_exact(std::max(F.lpar.cap, (size_t)fp.capVisit)));
-    }
+    fp.capVisit = bd.capVisit;
+    HIPCK(c, F.visit.reserve_exact(bd.resVisit));                         // (0 each without the layout)
+    HIPCK(c, F.lsize.reserve_exact(bd.resLsize));
+    HIPCK(c, F.lpos.reserve_exact(bd.resLpos));
+    HIPCK(c, F.lpar.reserve_exact(bd.resLpar));
     fp.lsize = F.lsize.p; fp.lpos = F.lpos.p; fp.lpar = F.lpar.p;
     HIPCK(c, F.lvl.reserve((size_t)fp.maxLevels * FR_LVL));
     HIPCK(c, F.tot.reserve((size_t)m));
     HIPCK(c, F.vbase.reserve((size_t)m + 1));
-    fp.visit = layoutOK ? (FVisit *)F.visit.p : nullptr; fp.lvl = F.lvl.p; fp.tot = F.tot.p; fp.vbase = F.vbase.p;
-    fp.sw = F.sw.p; fp.sa = F.sa.p; fp.sais = F.sais.p; fp.capE = capE;
-    fp.bw = F.bw.p; fp.ba = F.ba.p; fp.capBig = (long long)F.bw.cap; fp.bigSide = 0;
+    fp.visit = bd.layoutOK ? (FVisit *)F.visit.p : nullptr; fp.lvl = F.lvl.p; fp.tot = F.tot.p; fp.vbase = F.vbase.p;
+    fp.sw = F.sw.p; fp.sa = F.sa.p; fp.sais = F.sais.p; fp.capE = pl.capE;
+    fp.bw = F.bw.p; fp.ba = F.ba.p; fp.capBig = bd.capBig; fp.bigSide = 0;
     fp.ctr = (FCtr *)F.ctr.p; fp.S = (FSearch *)F.srch.p; fp.recs = (FRec *)F.recs.p;
-    fp.capRecs = (long long)(F.recs.cap / sizeof(FRec));
+    fp.capRecs = bd.capRecs;
     // trees with MAT local references: the lists a search carries go through the reference branches it crosses
     fp.mat = c->tree_has_mut ? 1 : 0;
     fp.mv = mview(c);
     fp.passList = nullptr; fp.capPass = 0; fp.passListR = nullptr; fp.capPassR = 0; fp.deferred = nullptr; fp.capDeferred = 0;
     if (fp.mat) {
-        HIPCK(c, F.passList.reserve_exact(std::max(F.passList.cap, (size_t)std::max<long long>(1 << 16, fp.capC / 8))));
+        HIPCK(c, F.passList.reserve_exact(bd.resPassList));
         fp.passList = F.passList.p; fp.capPass = (long long)F.passList.cap;
-        HIPCK(c, F.passListR.reserve_exact(std::max(F.passListR.cap, (size_t)std::max<long long>(1 << 16, (fp.capC - fp.capCC) / 4))));
+        HIPCK(c, F.passListR.reserve_exact(bd.resPassListR));
         fp.passListR = F.passListR.p; fp.capPassR = (long long)F.passListR.cap;
-        HIPCK(c, F.deferred.reserve_exact(F.passList.cap + F.passListR.cap));
+        HIPCK(c, F.deferred.reserve_exact(bd.resDeferred));
         fp.deferred = F.deferred.p; fp.capDeferred = (long long)F.deferred.cap;
     }
     if (dbgTime) fprintf(stderr, "[maple]   frontier +%.1f ms: pools reserved (%zu allocations, %.2f GB; free %.1f GB, room %.1f GB; per-lane scratch %lld x %d entries, shared %lld + %lld)\n", sinceEnter(),
-                         devbuf_stats().allocs - allocs0, 1e-9 * (double)(devbuf_stats().bytes - allocBytes0), 1e-9 * (double)freeB, 1e-9 * room,
-                         scratchLanes + extraSlabs, capE, capBig, capBig2);
+                         devbuf_stats().allocs - allocs0, 1e-9 * (double)(devbuf_stats().bytes - allocBytes0), 1e-9 * (double)in.freeBytes, 1e-9 * pl.room,
+                         pl.scratchLanes + pl.extraSlabs, pl.capE, pl.capBig, pl.capBig2);
     if (dbgTime)
         for (const PoolCap &pc : poolCaps)
             if (*pc.cap != pc.before) fprintf(stderr, "[maple]     %s: %.3f -> %.3f GB\n", pc.name, 1e-9 * (double)(pc.before * pc.elem), 1e-9 * (double)(*pc.cap * pc.elem));
@@ -1296,10 +1256,9 @@ int frontier_search(maple_ctx *c, const SearchParams &P, int m, const int32_t *n
     SearchOut *dout = (SearchOut *)F.out.p;
     DevTree T = c->dtree;
     const ArenaViewS av = view(c);
-    const int gridN = std::max(1, std::min(2048, (m + FR_BLOCK - 1) / FR_BLOCK));
     hipEvent_t e0, e1, er0, er1;
-    TRY(maple_internal_ev_pair(c, &e0, &e1, MAPLE_K_SPR_SEARCH, (double)m, 0.0));
-    const size_t slotEv = c->ev_used / 2 - 1;
+    size_t slotEv;
+    TRY(maple_internal_ev_pair(c, &e0, &e1, MAPLE_K_SPR_SEARCH, (double)m, 0.0, &slotEv));
     HIPCK(c, hipEventRecord(e0, s));
     // whole-tree searches whose rows of the dense score table are being made on another stream (FS_WIDE)
     std::vector<int32_t> wideIdx;
@@ -1330,7 +1289,7 @@ int frontier_search(maple_ctx *c, const SearchParams &P, int m, const int32_t *n
         HIPCK(c, hipGetLastError());
     }
     // (the seeding of a tree with local references writes lists through the lanes' scratch slabs: no more lanes than slabs)
-    DISPATCH3(c, k_fr_begin, <<<std::min(gridN, gridUpd), FR_BLOCK, 0, s>>>(c->d_model, av, T, P, m, F.nodes.p, fp, dout, budget, zeroBudget,
+    DISPATCH3(c, k_fr_begin, <<<std::min(pl.gridN, pl.gridUpd), FR_BLOCK, 0, s>>>(c->d_model, av, T, P, m, F.nodes.p, fp, dout, budget, zeroBudget,
                                                             anyWide ? F.wideRow.p : nullptr, anyWide ? wide->forceWide : 0,
                                                             overHint ? F.overHint.p : nullptr));
     HIPCK(c, hipGetLastError());
@@ -1338,17 +1297,6 @@ int frontier_search(maple_ctx *c, const SearchParams &P, int m, const int32_t *n
     FCtr hc;
     std::memset(&hc, 0, sizeof hc);
     int levels = 0;
-    // (many short-lived workgroups rather than a grid-stride loop over few long-lived ones: wavefront slots come free all the
-    // time, and the dispatcher hands them to the higher-priority stream first)
-    // (a launch of 16 384 workgroups costs 0.4-0.5 ms even when it finds ten thousand items: the grid goes with the batch -- a
-    // round's largest launch holds ~21 items per search)
-    const int gridCached = (int)std::min<long long>(16384, std::max<long long>(512, (long long)m / 12));
-    // items whose two lists add up to this many entries are walked by a wavefront each, in two size classes (frontier_dev.h):
-    // k_fr_updating_wave_s, sizeof(WaveUpdLds<128>) = 27 680 bytes of LDS per wavefront, five wavefronts per compute unit, and
-    // k_fr_updating_wave, sizeof(WaveUpdLds<512>) = 110 720 bytes, one per compute unit (+ 160 bytes of model constants each)
-    // (a handful of searches -- the re-search of a proposed move -- wait for every single item: all of them by wavefronts)
-    const int heavyMin = m <= 64 ? 1 : std::max(256, FR_HEAVY_MULT * (int)meanEnt / 4), gridWave = 256, gridWaveSmall = 1280;
-    const int bigMin = m <= 64 ? (1 << 30) : FR_BIG_MIN;                  // (lists of this many entries together: 16 items to a wavefront)
     std::vector<size_t> slotsC, slotsU;
     if (!F.side) {
         // (the cached-regime kernel's stream at the LOWEST priority: its kernel fills the GPU -- 128 registers x 4 wavefronts is a
@@ -1377,19 +1325,20 @@ int frontier_search(maple_ctx *c, const SearchParams &P, int m, const int32_t *n
     int launchesC = 0;
     auto u_level = [&]() -> int {                                          // the kernels of the open level, between events of their own
         hipEvent_t a0, a1;
-        TRY(maple_internal_ev_pair(c, &a0, &a1, MAPLE_K_FR_UPDATING, 0.0, 0.0));
-        slotsU.push_back(c->ev_used / 2 - 1);
+        size_t slot;
+        TRY(maple_internal_ev_pair(c, &a0, &a1, MAPLE_K_FR_UPDATING, 0.0, 0.0, &slot));
+        slotsU.push_back(slot);
         HIPCK(c, hipEventRecord(a0, s));
-        k_fr_sort_level<<<512, FR_BLOCK, 0, s>>>(av, T, fp, heavyMin, bigMin);
+        k_fr_sort_level<<<512, FR_BLOCK, 0, s>>>(av, T, fp, pl.heavyMin, pl.bigMin);
         TRY(stage("k_fr_sort_level"));
         // (the level's three kinds of list-updating items behind each other on this stream.  The 512-entry class on a stream of its
         // own was measured: 175 ms per round instead of 152 -- a third side stream shares a hardware queue with the cached-regime
         // kernel's and runs behind it.)
-        TRY(fr_launch_updating(c, s, gridUpd, av, T, P, fp, budget, heavyMin));
+        TRY(fr_launch_updating(c, s, pl.gridUpd, av, T, P, fp, budget, pl.heavyMin));
         TRY(stage("k_fr_updating"));
-        if (heavyMin > 0) {
-            TRY(fr_launch_updating_wave_small(c, s, gridWaveSmall, av, T, P, fp, budget, heavyMin, scratchLanes + 256));
-            TRY(fr_launch_updating_wave(c, s, gridWave, av, T, P, fp, budget, heavyMin, scratchLanes));
+        if (pl.heavyMin > 0) {
+            TRY(fr_launch_updating_wave_small(c, s, pl.gridWaveSmall, av, T, P, fp, budget, pl.heavyMin, pl.scratchLanes + 256));
+            TRY(fr_launch_updating_wave(c, s, pl.gridWave, av, T, P, fp, budget, pl.heavyMin, pl.scratchLanes));
         }
         TRY(stage("k_fr_updating_wave"));
         HIPCK(c, hipEventRecord(a1, s));
@@ -1403,8 +1352,9 @@ int frontier_search(maple_ctx *c, const SearchParams &P, int m, const int32_t *n
     bool passQueued = false;
     auto c_launch = [&]() -> int {
         hipEvent_t b0, b1;
-        TRY(maple_internal_ev_pair(c, &b0, &b1, MAPLE_K_FR_CACHED, 0.0, 0.0));
-        slotsC.push_back(c->ev_used / 2 - 1);
+        size_t slot;
+        TRY(maple_internal_ev_pair(c, &b0, &b1, MAPLE_K_FR_CACHED, 0.0, 0.0, &slot));
+        slotsC.push_back(slot);
         if (fp.mat && passQueued) HIPCK(c, hipStreamWaitEvent(s2, F.evJoin2, 0));      // (the deferred items of the launch before)
         k_fr_snap_c<<<1, 64, 0, s2>>>(fp.ctr, fp.capCC, fp.capPass, fp.capDeferred, fp.lvl, fp.maxLevels);
         HIPCK(c, hipEventRecord(b0, s2));
@@ -1414,12 +1364,12 @@ int frontier_search(maple_ctx *c, const SearchParams &P, int m, const int32_t *n
             HIPCK(c, hipEventRecord(F.evFork2, s2));
             HIPCK(c, hipStreamWaitEvent(s3, F.evFork2, 0));
             DISPATCH3(c, k_fr_pass_wave, <<<1024, FR_BLOCK, 0, s3>>>(c->d_model, av, T, fp));
-            DISPATCH3(c, k_fr_pass, <<<256, FR_BLOCK, 0, s3>>>(c->d_model, av, T, fpC, scratchLanes + 2048));
+            DISPATCH3(c, k_fr_pass, <<<256, FR_BLOCK, 0, s3>>>(c->d_model, av, T, fpC, pl.scratchLanes + 2048));
             HIPCK(c, hipEventRecord(F.evJoin2, s3));
             passQueued = true;
             TRY(stage("k_fr_pass"));
         }
-        DISPATCH3(c, k_fr_cached, <<<gridCached, FR_BLOCK, 0, s2>>>(c->d_model, av, anyWide ? Tw : T, P, fp, budget,
+        DISPATCH3(c, k_fr_cached, <<<pl.gridCached, FR_BLOCK, 0, s2>>>(c->d_model, av, anyWide ? Tw : T, P, fp, budget,
                                                                         anyWide ? F.wideRow.p : nullptr,
                                                                         anyWide ? wide->fin : FiniteRows{nullptr, nullptr, 0}));
         HIPCK(c, hipEventRecord(b1, s2));
@@ -1427,52 +1377,47 @@ int frontier_search(maple_ctx *c, const SearchParams &P, int m, const int32_t *n
         launchesC++;
         return MAPLE_OK;
     };
-    // (an error inside the loop leaves nothing in flight on either stream behind it)
-    auto bail = [&](int rc) { (void)hipStreamSynchronize(s); (void)hipStreamSynchronize(s2); (void)hipStreamSynchronize(s3); return rc; };
+    // (from here to the results on the host, an error leaves nothing in flight on any of the three streams behind it)
+    QuiesceOnExit quiesce{{s, s2, s3}};
     // the first level is opened (the seeds of k_fr_begin) and the cached stream let go
     k_fr_snap_u<<<1, 64, 0, s>>>(fp.ctr, fp.capU, fp.capC - fp.capCC, fp.capPassR, fp.lvl, fp.maxLevels);
-    if (hipGetLastError() != hipSuccess || hipEventRecord(F.evFork, s) != hipSuccess || hipStreamWaitEvent(s2, F.evFork, 0) != hipSuccess
-        || (anyWide && wide->rowsReady && hipStreamWaitEvent(s2, wide->rowsReady, 0) != hipSuccess))   // (k_fr_cached reads the rows' bitmaps)
-        return bail(fail(c, MAPLE_ERR_HIP, "frontier level loop: HIP error"));
-    // the host looks at the counters every few levels: a handful of searches (the re-search of a proposed move) is over after a few
-    // levels and each look costs them less than the levels it saves; a whole round runs ~20 updating levels
-    const int groupLevels = m <= 64 ? 2 : 8;
+    HIPCK(c, hipGetLastError());
+    HIPCK(c, hipEventRecord(F.evFork, s));
+    HIPCK(c, hipStreamWaitEvent(s2, F.evFork, 0));
+    if (anyWide && wide->rowsReady) HIPCK(c, hipStreamWaitEvent(s2, wide->rowsReady, 0));   // (k_fr_cached reads the rows' bitmaps)
     for (;;) {
-        for (int g = 0; g < groupLevels; g++) {
-            { const int rc_ = u_level(); if (rc_) return bail(rc_); }
-            for (int k2 = 0; k2 < 2; k2++) { const int rc_ = c_launch(); if (rc_) return bail(rc_); }
+        for (int g = 0; g < pl.groupLevels; g++) {
+            TRY(u_level());
+            for (int k2 = 0; k2 < 2; k2++) TRY(c_launch());
         }
-        if (hipGetLastError() != hipSuccess || hipMemcpyAsync(&hc, fp.ctr, sizeof(FCtr), hipMemcpyDeviceToHost, s) != hipSuccess
-            || hipStreamSynchronize(s) != hipSuccess)
-            return bail(fail(c, MAPLE_ERR_HIP, "frontier level loop: HIP error"));
+        HIPCK(c, hipGetLastError());
+        HIPCK(c, hipMemcpyAsync(&hc, fp.ctr, sizeof(FCtr), hipMemcpyDeviceToHost, s));
+        HIPCK(c, hipStreamSynchronize(s));
         if (hc.hiU == hc.loU) break;                                       // (the level that was just opened is empty)
-        if (levels > 100000) return bail(fail(c, MAPLE_ERR_FATAL, "frontier search did not terminate"));
+        if (levels > 100000) return fail(c, MAPLE_ERR_FATAL, "frontier search did not terminate");
     }
     // the cached-regime items that are left: launches until one has found nothing new behind its snapshot
     for (;;) {
-        for (int g = 0; g < groupLevels; g++) { const int rc_ = c_launch(); if (rc_) return bail(rc_); }
-        if (passQueued && hipStreamWaitEvent(s2, F.evJoin2, 0) != hipSuccess) return bail(fail(c, MAPLE_ERR_HIP, "frontier level loop: HIP error"));
-        if (hipGetLastError() != hipSuccess || hipMemcpyAsync(&hc, fp.ctr, sizeof(FCtr), hipMemcpyDeviceToHost, s2) != hipSuccess
-            || hipStreamSynchronize(s2) != hipSuccess)
-            return bail(fail(c, MAPLE_ERR_HIP, "frontier level loop: HIP error"));
+        for (int g = 0; g < pl.groupLevels; g++) TRY(c_launch());
+        if (passQueued) HIPCK(c, hipStreamWaitEvent(s2, F.evJoin2, 0));
+        HIPCK(c, hipGetLastError());
+        HIPCK(c, hipMemcpyAsync(&hc, fp.ctr, sizeof(FCtr), hipMemcpyDeviceToHost, s2));
+        HIPCK(c, hipStreamSynchronize(s2));
         const unsigned long long haveC = std::min<unsigned long long>(hc.usedC, (unsigned long long)fp.capCC),
                                  haveR = std::min<unsigned long long>(hc.usedR, (unsigned long long)(fp.capC - fp.capCC));
         if (hc.hiC == haveC && hc.hiR == haveR && hc.hiD == std::min<unsigned long long>(hc.nDeferred, (unsigned long long)fp.capDeferred)) break;
-        if (launchesC > 200000) return bail(fail(c, MAPLE_ERR_FATAL, "frontier search did not terminate"));
+        if (launchesC > 200000) return fail(c, MAPLE_ERR_FATAL, "frontier search did not terminate");
     }
-    if (hipEventRecord(F.evJoin, s2) != hipSuccess || hipStreamWaitEvent(s, F.evJoin, 0) != hipSuccess)
-        return bail(fail(c, MAPLE_ERR_HIP, "frontier level loop: HIP error"));
+    HIPCK(c, hipEventRecord(F.evJoin, s2));
+    HIPCK(c, hipStreamWaitEvent(s, F.evJoin, 0));
     if (dbgTime) fprintf(stderr, "[maple]   frontier +%.1f ms: expansion done (%d updating levels, %d cached launches)\n", sinceEnter(), levels, launchesC);
     size_t slotWide = (size_t)-1;
-    // (replay, refinement, final selection: an error in here must not return with kernels still in flight on either stream --
-    // the caller may reuse or free the pools -- so the stage is a lambda and its status goes through bail() like the loop's)
-    auto finishStage = [&]() -> int {
+    // replay, refinement, final selection
     if (anyWide) {
         // the whole-tree searches: the same exact walk, a wavefront each, the clades in the cached regime scanned over the rows
         // of the dense score table -- next to the other searches' walk (k_fr_replay: one lane each, as long as its longest search)
         hipEvent_t w0, w1;
-        TRY(maple_internal_ev_pair(c, &w0, &w1, MAPLE_K_FR_WIDE, 0.0, 0.0));
-        slotWide = c->ev_used / 2 - 1;
+        TRY(maple_internal_ev_pair(c, &w0, &w1, MAPLE_K_FR_WIDE, 0.0, 0.0, &slotWide));
         const int capB = 512, gridW = (int)std::min<size_t>(8192, wideIdx.size());
         HIPCK(c, F.wideBr.reserve_exact(std::max(F.wideBr.cap, (size_t)gridW * capB * sizeof(BestRec))));
         HIPCK(c, hipEventRecord(F.evFork, s));
@@ -1487,39 +1432,36 @@ int frontier_search(maple_ctx *c, const SearchParams &P, int m, const int32_t *n
     }
     TRY(maple_internal_ev_pair(c, &er0, &er1, MAPLE_K_FR_REPLAY, (double)m, 0.0));
     HIPCK(c, hipEventRecord(er0, s));
-    const int gridLayout = (int)std::min<long long>(1024, std::max<long long>(64, (long long)m / 64));   // (~100 small launches: the grid goes with the batch)
     if (levels <= fp.maxLevels && launchesC <= fp.maxLevels && fp.visit) {
         // the items of every search in the order its walk visits them: sizes bottom-up, ranks top-down, one record each
         HIPCK(c, hipMemsetAsync(fp.lpos, 0xFF, (size_t)fp.capVisit * sizeof(int32_t), s));   // (-1: not laid out)
-        for (int l = launchesC - 1; l >= 0; l--) k_fr_layout_sizes<<<gridLayout, FR_BLOCK, 0, s>>>(fp, l, 1);
-        for (int l = levels - 1; l >= 0; l--) k_fr_layout_sizes<<<gridLayout, FR_BLOCK, 0, s>>>(fp, l, 0);
-        k_fr_layout_totals<<<gridN, FR_BLOCK, 0, s>>>(m, fp);
+        for (int l = launchesC - 1; l >= 0; l--) k_fr_layout_sizes<<<pl.gridLayout, FR_BLOCK, 0, s>>>(fp, l, 1);
+        for (int l = levels - 1; l >= 0; l--) k_fr_layout_sizes<<<pl.gridLayout, FR_BLOCK, 0, s>>>(fp, l, 0);
+        k_fr_layout_totals<<<pl.gridN, FR_BLOCK, 0, s>>>(m, fp);
         k_fr_layout_scan<<<1, 1024, 0, s>>>(m, fp.tot, fp.vbase);
-        k_fr_layout_seeds<<<gridN, FR_BLOCK, 0, s>>>(m, fp);
-        for (int l = 0; l < levels; l++) k_fr_layout_place<<<gridLayout, FR_BLOCK, 0, s>>>(fp, l, 0);
-        for (int l = 0; l < launchesC; l++) k_fr_layout_place<<<gridLayout, FR_BLOCK, 0, s>>>(fp, l, 1);
+        k_fr_layout_seeds<<<pl.gridN, FR_BLOCK, 0, s>>>(m, fp);
+        for (int l = 0; l < levels; l++) k_fr_layout_place<<<pl.gridLayout, FR_BLOCK, 0, s>>>(fp, l, 0);
+        for (int l = 0; l < launchesC; l++) k_fr_layout_place<<<pl.gridLayout, FR_BLOCK, 0, s>>>(fp, l, 1);
         HIPCK(c, hipGetLastError());
         TRY(stage("k_fr_layout"));
     } else fp.visit = nullptr;
-    k_fr_replay<<<gridN, FR_BLOCK, 0, s>>>(P, m, fp, dout);
+    k_fr_replay<<<pl.gridN, FR_BLOCK, 0, s>>>(P, m, fp, dout);
     TRY(stage("k_fr_replay"));
     if (anyWide) HIPCK(c, hipStreamWaitEvent(s, F.evJoin, 0));
     if (anyWide && fp.mat && wide->nFrames > 0) {
-        DISPATCH3(c, k_fr_wide_frames, <<<std::min(gridUpd, 512), FR_BLOCK, 0, s>>>(c->d_model, av, T, fp, wide->frameParent, wide->frameNode));
+        DISPATCH3(c, k_fr_wide_frames, <<<std::min(pl.gridUpd, 512), FR_BLOCK, 0, s>>>(c->d_model, av, T, fp, wide->frameParent, wide->frameNode));
         TRY(stage("k_fr_wide_frames"));
     }
-    DISPATCH3(c, k_fr_refine, <<<gridUpd, FR_BLOCK, 0, s>>>(c->d_model, av, T, fp));
+    DISPATCH3(c, k_fr_refine, <<<pl.gridUpd, FR_BLOCK, 0, s>>>(c->d_model, av, T, fp));
     TRY(stage("k_fr_refine"));
-    k_fr_finish<<<gridN, FR_BLOCK, 0, s>>>(av, T, P, m, fp, dout, poolW, poolA, poolUsed, poolCapW, poolCapA);
+    k_fr_finish<<<pl.gridN, FR_BLOCK, 0, s>>>(av, T, P, m, fp, dout, poolW, poolA, poolUsed, poolCapW, poolCapA);
     HIPCK(c, hipGetLastError());
     HIPCK(c, hipEventRecord(er1, s));
     HIPCK(c, hipEventRecord(e1, s));
     HIPCK(c, hipMemcpyAsync(hostOut, dout, (size_t)m * sizeof(SearchOut), hipMemcpyDeviceToHost, s));
     HIPCK(c, hipMemcpyAsync(&hc, fp.ctr, sizeof(FCtr), hipMemcpyDeviceToHost, s));
     HIPCK(c, hipStreamSynchronize(s));
-    return MAPLE_OK;
-    };
-    { const int rc_ = finishStage(); if (rc_) return bail(rc_); }
+    quiesce.disarm();                                                      // (everything queued above is behind this stream's work)
     if (dbgTime) fprintf(stderr, "[maple]   frontier +%.1f ms: replay, refinement, final selection done; results on the host\n", sinceEnter());
     if (dbgTime && (hc.fbReason[0] | hc.fbReason[1] | hc.fbReason[2] | hc.fbReason[3] | hc.fbReason[4] | hc.fbReason[5] | hc.fbReason[6] | hc.fbReason[7]))
         fprintf(stderr, "[maple]   exact walk handed searches to the one-lane kernel: %d a merge within tolerance, %d a list re-expressed from a shortened one, "
@@ -1582,13 +1524,8 @@ int frontier_search(maple_ctx *c, const SearchParams &P, int m, const int32_t *n
                 wideIdx.size(), tw, mw, ts, ms, ns, mxn);
     }
 #endif
-    // (a batch of whole-tree searches only says nothing about the next full one -- and neither does a handful of searches: the
-    // re-searches of the apply phase, one to 32 at a time, used to leave their asks behind, the next ROUND scaled them up by
-    // 200 000 / 1 and grew the pools to whatever fitted: 1.8 s of hipMalloc in the first search after the moves, round 6)
-    if (!(anyWide && wide->forceWide) && (m >= 1024 || m >= F.needM)) {
-        F.needU = (long long)hc.usedU; F.needC = (long long)hc.usedC; F.needR = (long long)hc.usedR; F.needL = (long long)hc.nLists; F.needW = (long long)hc.usedW;
-        F.needA = (long long)hc.usedA; F.needM = m; F.lastOverflow = hc.overflow != 0;
-    }
+    // (whether this batch's asks replace the remembered ones: search_plan.h)
+    F.need = plan::remember_frontier(F.need, m, anyWide && wide->forceWide, hc.usedU, hc.usedC, hc.usedR, hc.nLists, hc.usedW, hc.usedA, hc.overflow != 0);
     F.lastU = std::min((long long)hc.usedU, fp.capU); F.lastC = std::min((long long)hc.usedC, fp.capCC);
     F.lastR = std::min((long long)hc.usedR, fp.capC - fp.capCC); F.lastPools = fp;
     {

@@ -1536,7 +1536,7 @@ extern "C" int maple_evaluate_placement_batch(maple_ctx *c, int32_t n, const int
 }
 
 // ---- device-resident forms ---------------------------------------------------------------------------
-int maple_internal_ev_pair(maple_ctx *c, hipEvent_t *a, hipEvent_t *b, int kind, double units, double bytes)
+int maple_internal_ev_pair(maple_ctx *c, hipEvent_t *a, hipEvent_t *b, int kind, double units, double bytes, size_t *slotOut)
 {
     if (c->ev_used >= 65536) c->ev_used = 0;      // nobody is reading these timings: recycle the event pairs
     const size_t slot = c->ev_used / 2;
@@ -1552,6 +1552,7 @@ int maple_internal_ev_pair(maple_ctx *c, hipEvent_t *a, hipEvent_t *b, int kind,
     *a = c->evs[c->ev_used];
     *b = c->evs[c->ev_used + 1];
     c->ev_used += 2;
+    if (slotOut) *slotOut = slot;
     return MAPLE_OK;
 }
 

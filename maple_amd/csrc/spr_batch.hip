@@ -29,6 +29,7 @@ using namespace maple;
 #include "batch_host.h"
 #include "frontier.h"
 #include "witness.h"
+#include "search_plan.h"
 
 // 248 VGPRs let only 2 wavefronts share a SIMD; the search is latency-bound, so capping it at 128 VGPRs (4 wavefronts,
 // some state spilled to scratch) is faster: deep round 134 -> 103 ms (3 waves 115, 5 waves 144, 8 waves 186).
@@ -36,20 +37,7 @@ using namespace maple;
 #define MAPLE_SPR_ATTR __attribute__((amdgpu_waves_per_eu(4, 4)))
 #endif
 // SPR regraft search: one lane = one query (state machine in search_dev.h) ---------------------------
-struct LaneBytes { size_t w, aux, h, st, best, ais, total; };
-static LaneBytes lane_bytes(const WsLayout &L)
-{
-    auto al = [](size_t x) { return (x + 63) & ~(size_t)63; };
-    LaneBytes b;
-    b.w = al((size_t)L.capW * sizeof(uint2));
-    b.aux = al((size_t)L.capA * sizeof(double));
-    b.h = al((size_t)L.capH * sizeof(TList));
-    b.st = al((size_t)L.capS * sizeof(StackItem));
-    b.best = al((size_t)L.capB * sizeof(BestRec));
-    b.ais = al((size_t)L.capAis * sizeof(double));
-    b.total = b.w + b.aux + b.h + b.st + b.best + b.ais;
-    return b;
-}
+struct LaneBytes { size_t w, aux, h, st, best, ais, total; };   // bytes of a lane's workspace, part by part (plan::plan_lane_launch)
 
 // ASSIST: with the wave-assisted lane searches compiled in.  A kernel of its own (k_spr_search_assisted): inlined next to the
 // rest, that path costs every launch registers (with an error model the whole kernel spilled four times as many, and the
@@ -1136,9 +1124,7 @@ extern "C" int maple_spr_search_batch(maple_ctx *c, int32_t n, const int32_t *no
     HIPCK(c, hipMemsetAsync(c->s_counter.p, 0, 8 * sizeof(int32_t), c->stream));
     unsigned long long *poolUsed = (unsigned long long *)(c->s_counter.p + 2);
     if (dbgT) fprintf(stderr, "[maple] t=%.1f ms: result records cleared\n", tms(tStart, tnow()));
-    // per-lane list workspace: a search near the root of a tree with long lists (rate variation: many O vectors) merges
-    // lists of several hundred entries a few hundred times before it is handed over or done
-    const int capW0 = ws_entries_per_lane > 0 ? ws_entries_per_lane : std::max(16384, 64 * c->tree_max_ent);
+    const int capW0 = plan::lane_cap_w0(ws_entries_per_lane, c->tree_max_ent);   // (per-lane list workspace)
     // Runs the searches `todo` (results into ho[slot[]]).  Queries whose per-lane workspace overflowed (status -3) are
     // re-run with 8x the workspace, twice at most.  cacheS (optional) = row-major (|todo| x T.n) cached scores.
     bool heavyQueries = false;
@@ -1168,8 +1154,7 @@ extern "C" int maple_spr_search_batch(maple_ctx *c, int32_t n, const int32_t *no
     std::function<int()> afterLaunch;                                  // called once, right after the next search kernel is queued
     auto run_queries = [&](std::vector<int32_t> todo, std::vector<int32_t> slot, const double *cacheS, int budgetNow,
                            const int32_t *rTable, int nF) -> int {
-        // the few cached (whole-tree) searches get room up front; more when the budgeted pass already ran out of it
-        int capW = cacheS ? (heavyQueries ? 8 : 4) * capW0 : capW0;
+        int capW = plan::lane_start_cap_w(capW0, cacheS != nullptr, heavyQueries);
         std::vector<int32_t> rows(todo.size());                        // row of each query in the cache / frame tables
         for (size_t k = 0; k < rows.size(); k++) rows[k] = rowOverride ? (*rowOverride)[k] : (int32_t)k;
         if ((int)c->h_depth.size() >= c->dtree.n) {
@@ -1204,54 +1189,21 @@ extern "C" int maple_spr_search_batch(maple_ctx *c, int32_t n, const int32_t *no
         }
         for (int attempt = 0; attempt < 3 && !todo.empty(); attempt++, capW *= 8) {
             const int m = (int)todo.size();
-            WsLayout L;
-            L.capW = capW;
-            L.capA = 5 * L.capW;                                        // O-vector-heavy lists (rate variation) carry up to 4-5 aux doubles per entry
-            L.capH = L.capW / 8 + 256;
-            L.capS = 1024 * (attempt + 1);
-            L.capB = (cacheS ? 4096 : 1024) * (attempt + 1);             // whole-tree (cached) searches short-list far more branches
-            L.capAis = 8192 * (attempt + 1);
-            LaneBytes LB = lane_bytes(L);
-            // lanes: one query per lane while they last; at most 4 wavefronts per SIMD (the kernel's occupancy) and a
-            // workspace footprint bounded to ~96 GB of the 288 GB
-            long long wsBudget = 96ll << 30;
-            {   // ... and to 70 % of what is free on the device right now (plus what this buffer already holds)
-                size_t freeB = 0, totalB = 0;
-                if (hipMemGetInfo(&freeB, &totalB) == hipSuccess) {
-                    const long long avail = (long long)((double)(freeB + c->s_search_ws.cap) * 0.7);
-                    if (avail < wsBudget) wsBudget = avail;
-                }
-            }
-            long long maxLanes = wsBudget / (long long)LB.total;
-            if (maxLanes > 4096 * 64) maxLanes = 4096 * 64;
-            // lanes pull searches from a counter: more wavefronts than the GPU holds at once (4 per SIMD) only cost workspace
-            if (cacheS && maxLanes > 8192) maxLanes = 8192;
-            if (maxLanes < 64) maxLanes = 64;
-            const int lanesWanted = (int)(m < maxLanes ? m : maxLanes);
-            // searching lanes per wavefront (measured at 20k queries: the long searches of a non-strict round like 2 lanes,
-            // 42 vs 46 ms with 1; the short ones of a strict round like 1, 31 vs 37 ms with 2; more is always worse)
-            // (at 200k queries with the budget of a 100 000-tip tree: 2 / 4 / 8 / 13 / 24 lanes -> 825 / 645 / 512 / 424 / 417 ms)
-            const int lanesDiv = P.strict ? 32768 : (lanesWanted > 65536 ? 8192 : 16384);
-            int activeLanes = (lanesWanted + lanesDiv - 1) / lanesDiv;
-            if (activeLanes < 1) activeLanes = 1;
-            if (activeLanes > 64) activeLanes = 64;
-            // wave-assisted lane searches (below): the wavefront serves its lanes' score requests one after the other, so few
-            // searching lanes per wavefront (100 000 tips, budget 2 132: 2 / 4 / 6 / 8 / 16 / 24 lanes -> 298 / 281 / 279 / 289 /
-            // 394 / 345 ms; without the assistance 375)
-            if (!cacheS && assistOK && assistFew && activeLanes > 4) activeLanes = 4;
-            int nWaves = (lanesWanted + activeLanes - 1) / activeLanes;
-            if (nWaves > 8192) nWaves = 8192;
-            const int lanes = nWaves * activeLanes;
+            // the launch's workspace and lanes: plan::plan_lane_launch (search_plan.h)
+            plan::LanePlanIn in;
+            in.m = m; in.attempt = attempt; in.capW = capW;
+            in.cached = cacheS != nullptr; in.strict = P.strict; in.assist = assistOK && assistFew;
+            size_t totalB = 0;
+            in.freeKnown = hipMemGetInfo(&in.freeBytes, &totalB) == hipSuccess;
+            in.wsCap = c->s_search_ws.cap;
+            static_assert(sizeof(TList) == 24 && sizeof(StackItem) == 32 && sizeof(BestRec) == 40, "tests/search_plan_main.cpp runs the plans with these");
+            in.szList = sizeof(TList); in.szStack = sizeof(StackItem); in.szBest = sizeof(BestRec);
+            const plan::LanePlan lp = plan::plan_lane_launch(in);
+            const WsLayout L{lp.capW, lp.capA, lp.capH, lp.capS, lp.capB, lp.capAis};
+            const LaneBytes LB{lp.w, lp.aux, lp.h, lp.st, lp.best, lp.ais, lp.total};
+            const int activeLanes = lp.activeLanes, nWaves = lp.nWaves, lanes = lp.lanes;
             const auto tWs0 = tnow();
-            {   // grow-only and at least doubling (a 20 GB hipMalloc costs ~0.7 s): batches of slowly growing size must not
-                // reallocate every time
-                size_t need = (size_t)lanes * LB.total;
-                if (need > c->s_search_ws.cap) {
-                    const size_t top = (size_t)maxLanes * LB.total;
-                    need = std::min(std::max(need, 2 * c->s_search_ws.cap), std::max(top, need));
-                }
-                HIPCK(c, c->s_search_ws.reserve_exact(need));
-            }
+            HIPCK(c, c->s_search_ws.reserve_exact(lp.reserve));
             if (dbgT) fprintf(stderr, "[maple]   workspace %d lanes x %zu B: reserve %.1f ms\n", lanes, (size_t)LB.total, tms(tWs0, tnow()));
             HIPCK(c, hipMemsetAsync(c->s_counter.p, 0, sizeof(int32_t), c->stream));
             TRY(h2d(c, c->s_i32[0], todo.data(), (size_t)m));
@@ -1287,8 +1239,8 @@ extern "C" int maple_spr_search_batch(maple_ctx *c, int32_t n, const int32_t *no
             }
             const int coopMaxHost = 8;                                      // (see k_spr_search: requests served one by one)
             hipEvent_t e0, e1;
-            TRY(ev_pair(c, &e0, &e1, cacheS ? MAPLE_K_SPR_REPLAY : MAPLE_K_SPR_SEARCH, (double)m, 0.0));
-            const size_t slotEv = c->ev_used / 2 - 1;                       // (this launch's timing record: filled in below)
+            size_t slotEv;                                                  // (this launch's timing record: filled in below)
+            TRY(ev_pair(c, &e0, &e1, cacheS ? MAPLE_K_SPR_REPLAY : MAPLE_K_SPR_SEARCH, (double)m, 0.0, &slotEv));
             HIPCK(c, hipEventRecord(e0, c->stream));
 #define MAPLE_SPR_LAUNCH_ARGS <<<launchWaves, 64, dynLds, c->stream>>>(c->d_model, view(c), mview(c), Tk, P, m, c->s_i32[0].p,          \
                                                                          L, LB, c->s_search_ws.p, c->s_counter.p, dout, poolW,     \

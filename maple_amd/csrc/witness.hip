@@ -184,8 +184,8 @@ int witness_score(maple_ctx *c, hipStream_t st, int nQ, const int32_t *qList, co
     HIPCK(c, W.witB.reserve((size_t)nC)); HIPCK(c, W.bcand.reserve((size_t)nC));
     HIPCK(c, W.qCnt.reserve((size_t)nQ)); HIPCK(c, W.qOff.reserve((size_t)nQ + 1));
     hipEvent_t e0, e1;
-    TRY(maple_internal_ev_pair(c, &e0, &e1, MAPLE_K_SPR_SCORE, 0.0, 0.0));
-    const size_t slot = c->ev_used / 2 - 1;
+    size_t slot;
+    TRY(maple_internal_ev_pair(c, &e0, &e1, MAPLE_K_SPR_SCORE, 0.0, 0.0, &slot));
     HIPCK(c, hipEventRecord(e0, st));
     HIPCK(c, hipMemsetAsync(W.hist.p, 0, (size_t)nB * sizeof(int32_t), st));
     HIPCK(c, hipMemsetAsync(W.cnt.p, 0, (size_t)nB * sizeof(int32_t), st));

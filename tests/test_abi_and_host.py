@@ -94,7 +94,7 @@ def test_pack_unpack_roundtrip(name):
 
 
 def _search_fixtures():
-    return sorted(f for f in os.listdir(GOLDEN) if f.startswith("search_"))
+    return sorted(f for f in os.listdir(GOLDEN) if f.startswith("search_") and f.endswith(".json.gz"))
 
 
 @pytest.mark.parametrize("fname", _search_fixtures())

@@ -16,7 +16,7 @@ import pytest
 from golden_util import GOLDEN, close, lists_match, model_args, ref_indices, tup
 
 pytestmark = pytest.mark.gpu
-NAMES = sorted(f[len("search_"):-len(".json.gz")] for f in os.listdir(GOLDEN) if f.startswith("search_"))
+NAMES = sorted(f[len("search_"):-len(".json.gz")] for f in os.listdir(GOLDEN) if f.startswith("search_") and f.endswith(".json.gz"))
 
 
 def load(name):

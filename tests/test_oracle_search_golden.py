@@ -9,7 +9,7 @@ import pytest
 from golden_util import GOLDEN, close, lists_match, model_args, ref_indices, tup
 from oracle.oracle_py import Oracle, OracleTree
 
-NAMES = sorted(f[len("search_"):-len(".json.gz")] for f in os.listdir(GOLDEN) if f.startswith("search_"))
+NAMES = sorted(f[len("search_"):-len(".json.gz")] for f in os.listdir(GOLDEN) if f.startswith("search_") and f.endswith(".json.gz"))
 
 
 @pytest.mark.parametrize("name", NAMES)
