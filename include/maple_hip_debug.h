@@ -58,6 +58,17 @@ int maple_debug_simplify_batch(maple_ctx *ctx, int32_t n, const double *vec4, co
  * functions into kernels of its own: it checks the source the search is built from, not the search's object code. */
 int maple_debug_frontier_pass_batch(maple_ctx *ctx, int32_t n, const int32_t *list, const int32_t *mutList, const uint8_t *dirIsUp,
                                     int32_t waveForm, int32_t *outList, uint8_t *grade, uint8_t *sameHandle);
+/* Rows of the score table of whole-tree SPR searches from explicit lists, by the launches maple_spr_search_batch makes them with:
+ * form 0 = the dense kernel with the bitmap of finite scores, form 1 = the witness filter (maple_amd/csrc/witness.hip: every
+ * qBLen must be 0 -- the caller's duty, as in the product -- and with an error model it returns MAPLE_ERR_STATE), then the bitmap's
+ * prefix counts.  nQ searches (removed lists qList, qTip, qBLen) against nC candidate lists (cand; -1 = a column without a list).
+ * out[nQ * ldOut] (ldOut >= nC) is filled with `fill` first; the score of (q, k) goes to out[q * ldOut + (outCol ? outCol[k] : k)]
+ * if it is finite and nowhere if it is -inf.  finMask[nQ * nWords], nWords = ceil(nC / 64): bit k % 64 of word k / 64 of row q set
+ * exactly for the finite scores; prefix[nQ * (nWords + 1)]: the set bits of the row before each word, then the row's total.
+ * *pairsWalked (optional): the (search, candidate) pairs form 1 walked, -1 for form 0. */
+int maple_debug_score_rows(maple_ctx *ctx, int32_t form, int32_t nQ, const int32_t *qList, const uint8_t *qTip, const double *qBLen,
+                           int32_t nC, const int32_t *cand, const int32_t *outCol /* or NULL */, int64_t ldOut, double fill, double *out,
+                           uint64_t *finMask, int32_t *prefix, int64_t *pairsWalked /* or NULL */);
 
 #ifdef __cplusplus
 }

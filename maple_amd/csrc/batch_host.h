@@ -141,3 +141,7 @@ int launch_place_score(maple_ctx *c, int nQ, int nF, const int32_t *qFrameLists,
 // the device tree once more from the host copy of its columns (after maple_tree_patch left tables stale)
 __attribute__((visibility("hidden")))
 int tree_rebuild_from_host(maple_ctx *c);
+// k_finite_prefix on stream st: prefix[row * (nWords + 1) + w] = the finite scores of the row before word w of its bitmap
+// mask[row * nWords ..], prefix[.. + nWords] = the row's total (FiniteRows, search_dev.h)
+__attribute__((visibility("hidden")))
+int launch_finite_prefix(maple_ctx *c, hipStream_t st, size_t rows, int nWords, const unsigned long long *mask, int32_t *prefix);

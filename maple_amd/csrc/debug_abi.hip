@@ -6,6 +6,7 @@
 #include "batch_host.h"
 #include "frontier.h"
 #include "frontier_dev.h"
+#include "witness.h"
 
 #include <algorithm>
 
@@ -339,4 +340,62 @@ extern "C" int maple_debug_frontier_pass_batch(maple_ctx *c, int32_t n, const in
         for (int i = 0; i < n; i++) if (sameHandle[i]) outList[i] = list[i];
     } while (0);
     return rc;
+}
+
+// ---- score rows of the whole-tree searches from explicit lists (spr_batch.hip's pre_rows makes them from a tree) --------------------
+// form 0: the dense kernel with bitmap (launch_append_queries(..., finMask)), form 1: the witness filter (witness_score); then the
+// prefix counts the replay kernels index by (launch_finite_prefix).  The product's launches on the caller's lists; only the fill of
+// the table beforehand is the hook's own -- the product leaves the cells of -inf scores as they are.
+__global__ __launch_bounds__(MAPLE_BLOCK) void k_debug_fill(long long n, double v, double *out)
+{
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) out[i] = v;
+}
+
+extern "C" int maple_debug_score_rows(maple_ctx *c, int32_t form, int32_t nQ, const int32_t *qList, const uint8_t *qTip, const double *qBLen,
+                                      int32_t nC, const int32_t *cand, const int32_t *outCol, int64_t ldOut, double fill, double *out,
+                                      uint64_t *finMask, int32_t *prefix, int64_t *pairsWalked)
+{
+    if (!c || form < 0 || form > 1 || nQ <= 0 || nC <= 0 || !qList || !qTip || !qBLen || !cand || ldOut < nC || !out || !finMask || !prefix)
+        return MAPLE_ERR_ARG;
+    if ((long long)nQ * ldOut > (1ll << 28)) return fail(c, MAPLE_ERR_ARG, "maple_debug_score_rows: a table of %lld scores", (long long)nQ * ldOut);
+    HIPCK(c, hipSetDevice(c->device));
+    TRY(need_model(c));
+    TRY(check_ids(c, nQ, qList, false, "qList"));
+    TRY(check_ids(c, nC, cand, true, "cand"));
+    for (int k = 0; k < nC; k++) {
+        if (cand[k] < -1) return fail(c, MAPLE_ERR_ARG, "cand[%d] = %d", k, cand[k]);
+        if (outCol && (outCol[k] < 0 || outCol[k] >= ldOut)) return fail(c, MAPLE_ERR_ARG, "outCol[%d] = %d is outside a row of %lld", k, outCol[k], (long long)ldOut);
+    }
+    TRY(settle(c));
+    const int nWords = (nC + 63) / 64;
+    const size_t nOut = (size_t)nQ * (size_t)ldOut, nMask = (size_t)nQ * nWords, nPre = (size_t)nQ * (nWords + 1);
+    DevBuf<double> dOut;
+    DevBuf<unsigned long long> dMask;
+    DevBuf<int32_t> dPre;
+    HIPCK(c, dOut.reserve_exact(nOut));
+    HIPCK(c, dMask.reserve_exact(nMask));
+    HIPCK(c, dPre.reserve_exact(nPre));
+    TRY(stage_begin(c, (size_t)nQ * 16 + (size_t)nC * 8 + 256));
+    STAGE(dq, c, qList, nQ); STAGE(dtip, c, qTip, nQ); STAGE(dbl, c, qBLen, nQ); STAGE(dcand, c, cand, nC);
+    const int32_t *dcol = nullptr;
+    if (outCol) { STAGE(dc, c, outCol, nC); dcol = dc; }
+    TRY(stage_flush(c));
+    hipLaunchKernelGGL(k_debug_fill, dim3(grid_for((int)nOut)), dim3(MAPLE_BLOCK), 0, c->stream, (long long)nOut, fill, dOut.p);
+    HIPCK(c, hipGetLastError());
+    // (both forms write every word of the bitmap themselves, and the prefix kernel every count: they start from a pattern)
+    HIPCK(c, hipMemsetAsync(dMask.p, 0xA5, nMask * sizeof(unsigned long long), c->stream));
+    HIPCK(c, hipMemsetAsync(dPre.p, 0xA5, nPre * sizeof(int32_t), c->stream));
+    long long pairs = -1;
+    if (form == 1)
+        TRY(witness_score(c, c->stream, nQ, dq, dtip, dbl, nC, dcand, dcol, dOut.p, ldOut, dMask.p, nWords, 0.0, 0.0, &pairs));
+    else
+        TRY(launch_append_queries(c, c->stream, nQ, dq, nC, dcand, 0, 0.0, dOut.p, ldOut, dcol, dtip, dbl, MAPLE_K_OTHER, 0.0, nullptr, nullptr,
+                                  nullptr, 0, 1, dMask.p));
+    TRY(launch_finite_prefix(c, c->stream, (size_t)nQ, nWords, dMask.p, dPre.p));
+    HIPCK(c, hipMemcpyAsync(out, dOut.p, nOut * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCK(c, hipMemcpyAsync(finMask, dMask.p, nMask * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    HIPCK(c, hipMemcpyAsync(prefix, dPre.p, nPre * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    if (pairsWalked) *pairsWalked = pairs;
+    return MAPLE_OK;
 }

@@ -1021,6 +1021,14 @@ __global__ __launch_bounds__(64) void k_finite_prefix(int nRows, int nWords, con
         }
     }
 }
+// (declared in batch_host.h: the round below and the score-row hook of debug_abi.hip share this launch)
+int launch_finite_prefix(maple_ctx *c, hipStream_t st, size_t rows, int nWords, const unsigned long long *mask, int32_t *prefix)
+{
+    if (!rows) return MAPLE_OK;
+    k_finite_prefix<<<(int)std::min<size_t>(rows, 4096), 64, 0, st>>>((int)rows, nWords, mask, prefix);
+    HIPCK(c, hipGetLastError());
+    return MAPLE_OK;
+}
 
 // Trees with MAT local references: lists up the chain of their frames (passGenomeListThroughBranch, one enclosing frame per
 // round, batched) until every one is written in the ROOT's frame.  ids / fr: list ids and their frames, both updated in place.
@@ -1145,11 +1153,7 @@ extern "C" int maple_spr_search_batch(maple_ctx *c, int32_t n, const int32_t *no
         return MAPLE_OK;
     };
     auto fin_prefix = [&](hipStream_t st, size_t row0, size_t rows) -> int {   // (after the dense launch that wrote those rows' bitmaps)
-        if (!rows) return MAPLE_OK;
-        k_finite_prefix<<<(int)std::min<size_t>(rows, 4096), 64, 0, st>>>((int)rows, finWords, c->s_fin_mask.p + row0 * finWords,
-                                                                          c->s_fin_prefix.p + row0 * (finWords + 1));
-        HIPCK(c, hipGetLastError());
-        return MAPLE_OK;
+        return launch_finite_prefix(c, st, rows, finWords, c->s_fin_mask.p + row0 * finWords, c->s_fin_prefix.p + row0 * (finWords + 1));
     };
     std::function<int()> afterLaunch;                                  // called once, right after the next search kernel is queued
     auto run_queries = [&](std::vector<int32_t> todo, std::vector<int32_t> slot, const double *cacheS, int budgetNow,

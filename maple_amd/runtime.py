@@ -32,7 +32,7 @@ EXPORTS = [
 # include/maple_hip_debug.h: measurement aids and test hooks, exported by libmaple_hip_debug.so only (Device(..., debug=True))
 DEBUG_EXPORTS = ["maple_debug_wave_append_batch", "maple_debug_trace_query", "maple_debug_trace_read", "maple_debug_calib_walk",
                  "maple_debug_calib_write", "maple_debug_gpv_batch", "maple_debug_simplify_batch", "maple_debug_frontier_levels",
-                 "maple_debug_frontier_pass_batch", "maple_debug_live_resources"]
+                 "maple_debug_frontier_pass_batch", "maple_debug_live_resources", "maple_debug_score_rows"]
 LIB_PATH_DEBUG = os.path.join(HERE, "libmaple_hip_debug.so")
 
 
@@ -583,6 +583,25 @@ class Device:
         self._ck(self.lib.maple_debug_frontier_pass_batch(self.h, n, _ptr(lists), _ptr(mutLists), _ptr(up), int(bool(wave_form)),
                                                           _ptr(out), _ptr(grade), _ptr(same)))
         return out, grade, same.astype(bool)
+
+    def debug_score_rows(self, form, q_lists, qTip, qBLen, cands, out_col=None, ld_out=None, fill=float("nan")):
+        """Rows of the whole-tree searches' score table from explicit lists (maple_debug_score_rows): form 0 the dense kernel with
+        bitmap, form 1 the witness filter.  Returns (out [nQ, ld_out] -- `fill` where no finite score was written --, finMask
+        uint64 [nQ, nWords], prefix int32 [nQ, nWords + 1], pairs walked or -1)."""
+        q_lists, cands = _i32(q_lists), _i32(cands)
+        nQ, nC = len(q_lists), len(cands)
+        ld = nC if ld_out is None else int(ld_out)
+        nW = (nC + 63) // 64
+        tip, bl = _u8(np.broadcast_to(qTip, nQ)), _f64(np.broadcast_to(qBLen, nQ))
+        col = None if out_col is None else _i32(out_col)
+        assert col is None or len(col) == nC
+        out = np.zeros((nQ, max(ld, 1)))
+        mask = np.zeros((nQ, nW), dtype=np.uint64)
+        prefix = np.zeros((nQ, nW + 1), dtype=np.int32)
+        pairs = C.c_int64(-1)
+        self._ck(self.lib.maple_debug_score_rows(self.h, int(form), nQ, _ptr(q_lists), _ptr(tip), _ptr(bl), nC, _ptr(cands), _ptr(col),
+                                                 C.c_int64(ld), C.c_double(fill), _ptr(out), _ptr(mask), _ptr(prefix), C.byref(pairs)))
+        return out, mask, prefix, pairs.value
 
     def debug_calib_walk(self, nbytes, repeats=1):
         ms = C.c_float()

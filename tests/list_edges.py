@@ -38,6 +38,19 @@ areVectorsDifferent, rootVector, findProbRoot, isMinorSequence), one per group o
   rootvec           lower lists with paths of 0, 1 and 3 mutated branches, bLen 0 and > 0, both values of isFromTip
   rootprob          root-frame lower lists: flagged R runs and nucleotides, several hundred O entries (carry-overs)
   minor             pairs of tip-like lists for isMinorSequence: every arm of the type ladder on both sides, O against O
+
+`witness_corpus(mode)` gives (queries, candidates) for the score rows of the whole-tree SPR searches (the witness filter of
+maple_amd/csrc/witness.hip and the dense kernel's bitmap form), in the modes without an error model, one family per arm of the
+filter's eligibility and range rules and per boundary of its bucket and bitmap arithmetic:
+
+  wit_sites          candidates whose only eligible entry is at site 1, 2, lRef - 1 or lRef; queries with every kind of entry there
+  wit_rarest         several eligible entries per candidate, common and rare ones, ties in rarity
+  wit_none           candidates without an eligible entry (stored lengths, O vectors, N, R only) and slots without a list (None)
+  wit_query_extremes N everywhere, tail-less R everywhere, more than 512 entries, an N run over hundreds of buckets
+  wit_rootframe      lists passed upwards through a reference branch by the oracle, on both sides
+  wit_random         rich random lists, queries with little coverage, candidates' own lists as queries
+
+`witness_may_exclude` states the filter's rule on the tuple grammar; `oracle_rows` gives the oracle's score of every pair.
 """
 import numpy as np
 
@@ -825,3 +838,307 @@ def struct_corpus(mode):
     return {"shorten_runs": fam_shorten_runs(rng, ref, u), "pass_edges": fam_pass_edges(rng, ref, u),
             "pass_random": fam_pass_random(rng, ref, u), "differ_edges": fam_differ_edges(rng, ref, u),
             "rootvec": fam_rootvec(rng, ref, u), "rootprob": fam_rootprob(rng, ref, u), "minor": fam_minor(rng, ref, u)}
+
+
+# ---- the score rows of the whole-tree searches (witness filter, maple_amd/csrc/witness.hip) --------------------------------
+# Candidates look like probVectTotUp lists, queries like lower lists; no mode has an error model (the filter refuses one).
+WITNESS_MODES = ("jc", "unrest", "ratevar", "zeroq")
+WITNESS_FAMILIES = ("wit_sites", "wit_rarest", "wit_none", "wit_query_extremes", "wit_rootframe", "wit_random")
+WIT_SITES = (1, 2, L_REF - 1, L_REF)                              # where wit_sites puts its candidates' only eligible entry
+
+
+def assemble(ref, specs):
+    """A list from (kind, first position, Builder arguments) in any order: kind is "nuc", "o" or "run"."""
+    b = Builder(ref, False)
+    for kind, p, kw in sorted(specs, key=lambda s: s[1]):
+        if kind == "nuc":
+            b.nuc(p, **kw)
+        elif kind == "o":
+            b.o(p, **kw)
+        else:
+            b.run(kw["typ"], p, kw["end"], d0=kw.get("d0"), d1=kw.get("d1"))
+    return b.done()
+
+
+def open_list(gl, rng):
+    """Every R or nucleotide entry without a stored length, or with a stored 0.0, gets one above 0: no site of the list can be a
+    zero-length mismatch."""
+    out = []
+    for e in gl:
+        d = float(rng.choice([1e-5, 2e-4, 1e-3]))
+        if e[0] <= 4 and len(e) == 2:
+            e = e + (d,)
+        elif e[0] <= 4 and e[2] == 0.0:
+            e = e[:2] + (d,) + e[3:]
+        out.append(e)
+    return out
+
+
+def windowed(gl, rng, n_win=3, width=120):
+    """The list with N outside a few windows (a sample with little coverage)."""
+    L = L_REF
+    starts = np.sort(rng.choice(np.arange(2, L - width, width + 5), size=n_win, replace=False))
+    keep = np.zeros(L + 2, dtype=bool)
+    for a in starts:
+        keep[int(a):int(a) + width] = True
+    out, pos = [], 0
+    for e in gl:
+        end = e[1] if e[0] in (4, 5) else pos + 1
+        p = pos + 1
+        while p <= end:                                            # the entry cut into pieces inside and outside the windows
+            q = p
+            while q < end and keep[q + 1] == keep[p]:
+                q += 1
+            if not keep[p] or e[0] == 5:
+                out.append((5, q))
+            else:
+                out.append(((e[0], q) + e[2:]) if e[0] == 4 else e)
+            p = q + 1
+        pos = end
+    return merge_n_runs(out)
+
+
+def lower_form(gl):
+    """The list without second lengths (the grammar of a lower list)."""
+    return [e[:3] if (e[0] <= 4 and len(e) == 4) else e for e in gl]
+
+
+def fam_wit_sites(rng, ref):
+    L = len(ref)
+    qs, cs = [], []
+    for i, s in enumerate(WIT_SITES):
+        r = int(ref[s - 1])
+        x = other(rng, r)
+        y = other(rng, r, (x,))
+        z = other(rng, r, (x, y))
+        far = 700 + 10 * i                                         # (an entry that is not eligible, far from s)
+        cs.append(assemble(ref, [("nuc", s, dict(nuc=x))]))
+        cs.append(assemble(ref, [("nuc", s, dict(nuc=x)), ("nuc", far, dict(nuc=other(rng, int(ref[far - 1])), d0=1e-4, d1=2e-4))]))
+        cs.append(assemble(ref, [("nuc", s, dict(nuc=y))]))
+        cs.append(assemble(ref, [("nuc", s, dict(nuc=y)), ("o", far + 1, dict(vec=rng.dirichlet([1.0] * 4), d0=1e-4)),
+                                 ("run", far + 3, dict(typ=5, end=far + 9))]))
+        d = [1e-5, 2e-4, 1e-3, 3e-4][i]
+        q = lambda *specs: qs.append(assemble(ref, list(specs)))   # noqa: E731
+        mid = ("run", 3, dict(typ=5, end=L - 2))                   # (N between the four sites: the site alone decides)
+        q(("nuc", s, dict(nuc=x)), mid)                            # the same nucleotide: walked, finite
+        q(("nuc", s, dict(nuc=z)), mid)                            # another nucleotide: excluded
+        if s < L:                                                  # tail-less R up to the site, lengths after it: excluded
+            q(("run", 1, dict(typ=4, end=s)), ("run", s + 1, dict(typ=4, end=L, d0=d)))
+        else:
+            q(("run", 1, dict(typ=4, end=L)))
+        if s > 1:                                                  # lengths up to the site, tail-less R from it on: excluded
+            q(("run", 1, dict(typ=4, end=s - 1, d0=d)), ("run", s, dict(typ=4, end=L)))
+        q(("run", 1, dict(typ=4, end=2, d0=d)), mid, ("run", L - 1, dict(typ=4, end=L, d0=d)))   # R with d0 > 0 over it: walked, finite
+        q(("run", 1, dict(typ=4, end=2, d0=d, d1=2 * d)), mid, ("run", L - 1, dict(typ=4, end=L, d0=d, d1=2 * d)))   # ... with d0 and d1
+        if s > 1:                                                  # an N run that ends one site before it: excluded
+            q(("run", 1, dict(typ=5, end=s - 1)))
+        if s < L:                                                  # ... that starts one site after it: excluded
+            q(("run", s + 1, dict(typ=5, end=L)))
+        q(("run", s, dict(typ=5, end=s)))                          # N on exactly the site: walked
+        q(("o", s, dict(vec=o_vec(rng, x, 0.3))), mid)             # an O entry on it: walked
+        q(("o", s, dict(vec=o_vec(rng, y, 0.0), d0=d)), mid)       # ... with a length, nothing for y
+        q(("nuc", s, dict(nuc=z, d0=d)), mid)                      # another nucleotide with d0 > 0: walked, finite
+        q(("nuc", s, dict(nuc=z, d0=0.0)), mid)                    # ... with a stored 0.0: walked, -inf
+        q(("nuc", s, dict(nuc=x, d0=0.0)), mid)                    # the same with a stored 0.0
+    return qs, cs
+
+
+def fam_wit_rarest(rng, ref, n=48):
+    """Candidates with eligible entries at three common sites (shared by most) and at a rare one (shared by one or two)."""
+    L = len(ref)
+    common = [(300, other(rng, int(ref[299]))), (600, other(rng, int(ref[599]))), (601, other(rng, int(ref[600])))]
+    rare_of, nuc_at, cs, qs = [], {}, [], []
+    for k in range(n):
+        has = [True, k % 4 != 0, k % 2 == 0]
+        if k >= n - 4:
+            has = [True, True, False]                              # common entries only: the rarer of the two is the witness
+            rare = []
+        elif k % 6 == 5:                                           # two rare entries of its own: equally rare, the first is taken
+            rare = [900 + 4 * k, 902 + 4 * k]
+        else:
+            rare = [900 + 4 * (k - k % 2 if (k // 2) % 2 == 0 else k)]      # (every other pair of candidates shares its rare entry)
+        rare = [(p, nuc_at.setdefault(p, other(rng, int(ref[p - 1])))) for p in rare]
+        rare_of.append(rare)
+        specs = [("nuc", p, dict(nuc=x)) for (p, x), h in zip(common, has) if h] + [("nuc", p, dict(nuc=x)) for p, x in rare]
+        if k % 5 == 0:                                             # (an entry that is not eligible in between)
+            specs.append(("nuc", 450, dict(nuc=other(rng, int(ref[449])), d0=1e-4)))
+        cs.append(assemble(ref, specs))
+    com = [("nuc", p, dict(nuc=x)) for p, x in common]
+    for k in (1, 2, 5, 6, 11, 12):
+        mine = [("nuc", p, dict(nuc=x)) for p, x in rare_of[k]]
+        qs.append(assemble(ref, mine + com[1:]))                   # agrees with the rare entry, tail-less R at site 300
+        qs.append(assemble(ref, mine + com))                       # agrees with every entry
+        qs.append(assemble(ref, list(com)))                        # contradicts the rare entry only
+        qs.append(assemble(ref, mine + [("run", 250, dict(typ=5, end=650))]))          # N over the common sites
+    qs.append(assemble(ref, [("run", 250, dict(typ=5, end=L - 100))]))
+    qs.append(open_list(assemble(ref, com[:1]), rng))
+    return qs, cs
+
+
+def fam_wit_none(rng, ref):
+    """Candidates without an eligible entry (bucket 0: every search walks them) and the slots without a list (None)."""
+    L = len(ref)
+    nuc = lambda p, **kw: ("nuc", p, dict(nuc=other(rng, int(ref[p - 1])), **kw))      # noqa: E731
+    cs = [[(4, L)],
+          assemble(ref, [nuc(1, d0=0.0), nuc(400, d0=0.0), nuc(L, d0=0.0)]),
+          assemble(ref, [nuc(10, d0=0.0), nuc(11, d0=1e-4)]),
+          assemble(ref, [nuc(2, d0=1e-4), nuc(800, d0=3e-4), nuc(L - 1, d0=1e-5)]),
+          assemble(ref, [nuc(200, d0=2e-4), nuc(201, d0=2e-4)]),
+          assemble(ref, [nuc(1, d0=0.0, d1=1e-4), nuc(L, d0=1e-4, d1=0.0)]),
+          assemble(ref, [nuc(500, d0=1e-4, d1=2e-4), nuc(900, d0=1e-5, d1=1e-5)]),
+          None,
+          assemble(ref, [("o", 1, dict(vec=rng.dirichlet([1.0] * 4))), ("o", 640, dict(vec=rng.dirichlet([1.0] * 4), d0=1e-4)),
+                         ("o", L, dict(vec=rng.dirichlet([1.0] * 4)))]),
+          assemble(ref, [("o", p, dict(vec=rng.dirichlet([1.0] * 4))) for p in range(63, 67)]),
+          [(5, L)],
+          assemble(ref, [("run", 1, dict(typ=5, end=40)), ("run", 700, dict(typ=5, end=1100)), ("run", L, dict(typ=5, end=L))]),
+          None,
+          assemble(ref, [("run", 1, dict(typ=4, end=L, d0=1e-4, d1=2e-4))]),
+          assemble(ref, [("run", 1, dict(typ=4, end=750, d0=0.0)), ("run", 751, dict(typ=4, end=L, d0=1e-4))]),
+          None]
+    qs = [random_list(rng, ref, False, n, tails=False) for n in (1, 4, 9)]             # no lengths: -inf against a tail-less R
+    qs += [open_list(random_list(rng, ref, False, n, tails=False), rng) for n in (2, 7)]
+    qs.append(assemble(ref, [nuc(1), nuc(L)]))
+    qs.append(assemble(ref, [("run", 1, dict(typ=5, end=40)), nuc(41), ("run", 700, dict(typ=5, end=1100))]))
+    qs.append(assemble(ref, [("o", 64, dict(vec=rng.dirichlet([1.0] * 4))), ("o", 640, dict(vec=rng.dirichlet([1.0] * 4), d0=2e-4))]))
+    return qs, cs
+
+
+def fam_wit_query_extremes(rng, ref):
+    L = len(ref)
+    many = [("nuc", p, dict(nuc=other(rng, int(ref[p - 1])), d0=(None if p % 3 else 1e-4))) for p in range(2, 602)]
+    assert len(many) > 512
+    qs = [[(5, L)],                                                # N everywhere: walks every candidate
+          [(4, L)],                                                # tail-less R everywhere: walks bucket 0 only
+          assemble(ref, many),
+          assemble(ref, [("nuc", 50, dict(nuc=other(rng, int(ref[49])))), ("run", 100, dict(typ=5, end=1400))]),
+          assemble(ref, [("run", 1, dict(typ=4, end=99, d0=1e-4)), ("run", 100, dict(typ=5, end=1400)),
+                         ("run", 1401, dict(typ=4, end=L, d0=2e-4))])]
+    return qs, []
+
+
+def fam_wit_rootframe(mode):
+    """The upward cases of struct_corpus's pass_edges / pass_random through the oracle's passGenomeListThroughBranch: lists with
+    the entries a re-expression in an enclosing frame leaves behind (what lists_to_root_frame hands the filter), on both sides."""
+    from oracle.oracle_py import Oracle
+    o = Oracle(reference(), ROOT_FREQS)
+    o.set_model(**model(mode))
+    sc = struct_corpus(mode)
+    cases = [c for f in ("pass_edges", "pass_random") for c in sc[f] if c["dirIsUp"]]
+    res = [o.passGenomeListThroughBranch(c["pv"], c["mutations"], True) for c in cases]
+    return res[1::3], res
+
+
+def fam_wit_random(rng, ref, n=70):
+    cs = [rich_list(rng, ref, False, mean_gap=[15, 40, 100][k % 3]) for k in range(n)]
+    qs = [rich_list(rng, ref, False, mean_gap=[15, 40, 100][k % 3], d1=False) for k in range(8)]
+    qs += [open_list(rich_list(rng, ref, False, mean_gap=[15, 40, 100][k % 3], d1=False), rng) for k in range(4)]
+    qs += [windowed(open_list(rich_list(rng, ref, False, mean_gap=[8, 15, 40][k % 3], d1=False), rng), rng, *[(3, 120), (2, 40), (1, 25)][k % 3])
+           for k in range(21)]
+    qs += [lower_form(cs[k]) for k in range(1, n, 7)]              # a candidate's own list: agrees with each of its entries
+    return qs, cs
+
+
+_WIT_FAMILIES = {}
+
+
+def witness_families(mode):
+    """{family: (queries, candidates)} of a mode, built once (a candidate None is a slot without a list, id -1)."""
+    if mode not in _WIT_FAMILIES:
+        assert mode in WITNESS_MODES
+        ref = reference()
+        rng = np.random.default_rng(400 + MODES.index(mode))
+        _WIT_FAMILIES[mode] = {"wit_sites": fam_wit_sites(rng, ref), "wit_rarest": fam_wit_rarest(rng, ref),
+                               "wit_none": fam_wit_none(rng, ref), "wit_query_extremes": fam_wit_query_extremes(rng, ref),
+                               "wit_rootframe": fam_wit_rootframe(mode), "wit_random": fam_wit_random(rng, ref)}
+    return _WIT_FAMILIES[mode]
+
+
+def witness_corpus(mode):
+    """(queries, candidates): the families of witness_families(mode) one after the other, in the order of WITNESS_FAMILIES."""
+    fams = witness_families(mode)
+    return [q for f in WITNESS_FAMILIES for q in fams[f][0]], [c for f in WITNESS_FAMILIES for c in fams[f][1]]
+
+
+def witness_family_ranges(mode):
+    """{family: (range of its queries, range of its candidates)} within witness_corpus(mode)."""
+    out, q0, c0 = {}, 0, 0
+    for f in WITNESS_FAMILIES:
+        qs, cs = witness_families(mode)[f]
+        out[f] = (range(q0, q0 + len(qs)), range(c0, c0 + len(cs)))
+        q0, c0 = q0 + len(qs), c0 + len(cs)
+    return out
+
+
+# The rule of witness.hip's header, stated on the tuple grammar (not the library's code): a candidate entry is ELIGIBLE if it is a
+# nucleotide other than the reference's without a stored length; a search's list contradicts it if, at the entry's site, it holds
+# another nucleotide or the reference, again without a stored length.  Over a removed branch of length 0 and without an error
+# model appendProbNode of such a pair is -inf.
+ARMS = ("N", "O", "lengths", "same_nucleotide", "other_nucleotide", "reference")
+_ARM_N, _ARM_O, _ARM_LEN, _ARM_R = 5, 6, 7, 4
+
+
+def witness_eligible(cand_list):
+    """[(site, nucleotide)] of the eligible entries of a candidate list."""
+    return [(p, e[0]) for p, e in sites_of(cand_list) if e[0] < 4 and len(e) == 2 and e[0] != e[1]]
+
+
+def witness_arms(query_list, lengthless=lambda e: len(e) == 2):
+    """Per site (index = position), what a search's list holds there: 0-3 a nucleotide without a stored length, 4 the reference
+    without one, 5 N, 6 an O vector, 7 a nucleotide or the reference with lengths attached."""
+    arm = np.zeros(L_REF + 1, dtype=np.int8)
+    pos = 0
+    for e in query_list:
+        end = e[1] if e[0] in (4, 5) else pos + 1
+        arm[pos + 1:end + 1] = _ARM_N if e[0] == 5 else _ARM_O if e[0] == 6 else (e[0] if lengthless(e) else _ARM_LEN)
+        pos = end
+    assert pos == L_REF
+    return arm
+
+
+_WIT_VIEWS = {}
+
+
+def _wit_view(gl, fn):
+    key = (id(gl), fn.__name__)
+    if key not in _WIT_VIEWS:
+        _WIT_VIEWS[key] = (gl, fn(gl))                            # (the list is kept: its id stays its own)
+    return _WIT_VIEWS[key][1]
+
+
+def witness_may_exclude(cand_list, query_list, counts=None):
+    """May the pair be left out of the walk -- does ANY eligible entry of the candidate meet a contradicting entry of the search's
+    list?  (The library picks one witness per candidate: what it excludes is a subset.)  counts, a dict, takes the arm of every
+    eligible entry met ("no_eligible" for a candidate without one or a slot without a list)."""
+    elig = _wit_view(cand_list, witness_eligible) if cand_list is not None else []
+    arm = _wit_view(query_list, witness_arms)
+    if counts is not None and not elig:
+        counts["no_eligible"] = counts.get("no_eligible", 0) + 1
+    excl = False
+    for p, x in elig:
+        a = int(arm[p])
+        name = {_ARM_N: "N", _ARM_O: "O", _ARM_LEN: "lengths", _ARM_R: "reference"}.get(a, "same_nucleotide" if a == x else "other_nucleotide")
+        if counts is not None:
+            counts[name] = counts.get(name, 0) + 1
+        excl = excl or name in ("other_nucleotide", "reference")
+    return excl
+
+
+def witness_matrix(queries, cands, counts=None):
+    """witness_may_exclude of every pair: bool [len(queries), len(cands)]."""
+    return np.array([[witness_may_exclude(c, q, counts) for c in cands] for q in queries], dtype=bool).reshape(len(queries), len(cands))
+
+
+def oracle_rows(o, queries, cands, qTip, qBLen):
+    """appendProbNode(candidate, query, qTip[q], qBLen[q]) of every pair by the oracle `o` (its model set): float64
+    [len(queries), len(cands)], -inf in the column of a candidate None."""
+    nQ, nC = len(queries), len(cands)
+    have = [k for k, c in enumerate(cands) if c is not None]
+    packed = o.pack_many([cands[k] for k in have] + list(queries))
+    pi = np.tile(np.arange(len(have)), nQ)
+    qi = np.repeat(np.arange(nQ), len(have))
+    tip = np.broadcast_to(qTip, nQ)[qi]
+    bl = np.broadcast_to(np.asarray(qBLen, dtype=np.float64), nQ)[qi]
+    want = np.full((nQ, nC), -np.inf)
+    want[:, have] = o.appendProbNode_batch(packed, pi, len(have) + qi, tip, bl).reshape(nQ, len(have))
+    return want

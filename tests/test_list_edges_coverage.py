@@ -112,6 +112,10 @@ def test_corpus_follows_the_grammar():
         qs, cs = le.dense_lists(mode) if not mode.startswith("zeroq") else ([], [])
         for gl in qs + cs:
             le.check_grammar(gl, le.L_REF, u)
+    for mode in le.WITNESS_MODES:
+        qs, cs = le.witness_corpus(mode)
+        for gl in qs + [c for c in cs if c is not None]:
+            le.check_grammar(gl, le.L_REF, False)
     for mode in le.MODES[:5]:
         u = bool(le.model(mode).get("usingErrorRate"))
         for fam, cases in le.struct_corpus(mode).items():
@@ -259,3 +263,78 @@ def test_golden_calls_leave_these_branches_at_zero(counting_lib):
     zero = {k for k, v in total.items() if v == 0}
     print("\ngolden calls leave at 0:", sorted(zero))
     assert zero == GOLDEN_ZERO, (sorted(zero), total)
+
+
+# ---- the corpus of the whole-tree searches' score rows (witness filter, maple_amd/csrc/witness.hip) ------------------------------
+@pytest.fixture(scope="module")
+def witness_ref():
+    """mode -> (queries, candidates, the rule's answer per pair, its arm counts, the oracle's scores per isTipC), made once."""
+    o = Oracle(le.reference(), le.ROOT_FREQS)
+    cache = {}
+
+    def get(mode):
+        if mode not in cache:
+            o.set_model(**le.model(mode))
+            qs, cs = le.witness_corpus(mode)
+            counts = {}
+            excl = le.witness_matrix(qs, cs, counts)
+            cache[mode] = (qs, cs, excl, counts, {tip: le.oracle_rows(o, qs, cs, tip, 0.0) for tip in (False, True)})
+        return cache[mode]
+    return get
+
+
+@pytest.mark.parametrize("mode", le.WITNESS_MODES)
+def test_witness_rule_is_sound_against_the_oracle(witness_ref, mode):
+    """The proof in witness.hip's header, tested: a pair the rule may leave out scores -inf by the oracle, over a removed branch
+    of length 0, for both values of isTipC -- and the rule that takes an entry WITH a stored length for one without is caught."""
+    qs, cs, excl, counts, want = witness_ref(mode)
+    for tip in (False, True):
+        bad = excl & np.isfinite(want[tip])
+        assert not bad.any(), (mode, tip, np.argwhere(bad)[:5])
+    rq, rc = le.witness_family_ranges(mode)["wit_sites"]
+    wrong = 0
+    for q in rq:
+        arm = le.witness_arms(qs[q], lengthless=lambda e: True)    # (the mutant: d0 ignored)
+        for k in rc:
+            if any(arm[p] != x for p, x in le.witness_eligible(cs[k])) and np.isfinite(want[False][q, k]):
+                wrong += 1
+    assert wrong > 0
+
+
+@pytest.mark.parametrize("mode", le.WITNESS_MODES)
+def test_witness_corpus_reaches_every_arm(witness_ref, mode):
+    qs, cs, excl, counts, want = witness_ref(mode)
+    assert set(le.witness_families(mode)) == set(le.WITNESS_FAMILIES)
+    assert 180 <= len(cs) <= 220 and len(cs) % 64 != 0 and 130 <= len(qs) <= 170, (len(qs), len(cs))
+    for arm in le.ARMS + ("no_eligible",):                         # every arm of wit_ranges, and bucket 0
+        assert counts.get(arm, 0) > 0, (mode, arm, counts)
+    elig = [le.witness_eligible(c) if c is not None else [] for c in cs]
+    assert sum(c is None for c in cs) >= 2 and sum(c is not None and not e for c, e in zip(cs, elig)) >= 8
+    sites = {p for e in elig for p, _ in e}
+    assert {1, 2, le.L_REF - 1, le.L_REF} <= sites                 # the first and the last bucket of a nucleotide
+    only = [e[0] for e in elig if len(e) == 1]                     # candidates whose bucket is known without the histogram
+    assert len(only) > len(set(only))                              # ... two of them in one bucket
+    assert any(len(e) > 1 for e in elig)
+    ne = [len(q) for q in qs]
+    assert max(ne) > 512 and [(5, le.L_REF)] in qs and [(4, le.L_REF)] in qs
+    arms = [le.witness_arms(q) for q in qs]
+    assert max(int((a[1:] == 5).sum()) for a in arms if not (a[1:] == 5).all()) > 400     # an N run over hundreds of buckets
+
+
+@pytest.mark.parametrize("mode", le.WITNESS_MODES)
+def test_witness_corpus_is_balanced(witness_ref, mode):
+    """Conditions on the inputs, by the oracle alone: every family has pairs of both outcomes, a quarter of all pairs are finite,
+    a quarter may be left out by the rule, and at least 20 are -inf without any witness saying so (they must be walked, and
+    their bit must stay clear)."""
+    qs, cs, excl, counts, want = witness_ref(mode)
+    for tip in (False, True):
+        fin = np.isfinite(want[tip])
+        for fam, (rq, rc) in le.witness_family_ranges(mode).items():
+            if fam == "wit_query_extremes":
+                continue
+            sub = fin[np.ix_(list(rq), list(rc))]
+            assert sub.any() and not sub.all(), (mode, fam)
+        assert fin.mean() >= 0.25, (mode, fin.mean())
+        assert excl.mean() >= 0.25, (mode, excl.mean())
+        assert int((~fin & ~excl).sum()) >= 20
+        assert not np.isnan(want[tip]).any() and not np.isposinf(want[tip]).any()
