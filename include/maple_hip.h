@@ -356,6 +356,28 @@ int maple_placement_supports_batch(maple_ctx *ctx, int32_t nQ, const int32_t *qL
                                    int64_t *outOff, int32_t *outNode, double *outSupport, double *outBlen3,
                                    int32_t *bestTotalLh, int32_t *status);
 
+/* ---- expectation maximisation of the rates (expectationMaximizationCalculationRates, M:10077-10947; trackMutations=False) ----
+ * Both calls run on the tree of the last maple_tree_upload / maple_tree_patch and the model of the last maple_set_model
+ * (MAPLE_ERR_STATE without either), join the traversal made ahead by maple_placement_ahead first and leave its rows alone; their
+ * temporaries live under an arena mark of the library's own, released before they return.  nMinor[v] = len(minorSequences[v])
+ * for every node (NULL = all 0); a leaf is a node without children (nodeIsLeaf, M:10140 -- not isTip).
+ * One lane walks each branch (maple_amd/csrc/em.hip).  The totals are reduced in a fixed order (no float atomics: the same bits on
+ * every call) and the whole-number statistics with integer atomics (exact); the float per-site tables are accumulated with fp64
+ * atomic adds, so their last bits -- and those of the site rates and site error rates made from them -- can differ from call to
+ * call. */
+typedef struct { double counts[16], waitingTimes[4], errorCount, totTreeLength;
+                 int64_t observedTotNucsSites, numTips; } maple_em_totals;
+/* expectation: the sufficient statistics of M:10113-10136 after the walk of M:10138-10850, before M:10852 (tables the current
+ * model does not have come back as zeros) */
+int maple_em_expectation(maple_ctx *ctx, const int32_t *nMinor /* [n], NULL = 0 */, maple_em_totals *tot,
+                         double *waitingTimesSites /* [lRef*4] */, double *countsSites /* [lRef] */, double *trackingNs /* [lRef+1] */,
+                         double *observedNucsSites /* [lRef+1] */, double *errorCountSites /* [lRef] */);   /* per-site pointers may be NULL */
+/* the whole step, M:10077-10947: model 0 = UNREST, 1 = GTR (another value without an error model: MAPLE_ERR_ARG, the raise of
+ * M:10877); siteRates [lRef] / errorRateGlobal / siteErrRates [lRef] may be NULL where the current model has none; a negative
+ * probability where the reference raises (M:10293 and its kin): MAPLE_ERR_FATAL */
+int maple_em_rates(maple_ctx *ctx, const int32_t *nMinor, int model, double *Q16, double *siteRates,
+                   double *errorRateGlobal, double *siteErrRates);
+
 /* ---- device-resident forms (inputs already in HBM; asynchronous on `stream`) ---
  * `stream` is the caller's hipStream_t, used verbatim: NULL is the legacy default stream (what
  * torch.cuda.current_stream().cuda_stream is unless the caller switched streams), so the launch is ordered with the

@@ -438,6 +438,7 @@ extern "C" int maple_tree_upload(maple_ctx *c, int32_t n, int32_t root, const in
     c->h_tree_totUp.assign(totUp, totUp + n);
     c->h_tree_upRight.assign(upRight, upRight + n);
     c->h_tree_upLeft.assign(upLeft, upLeft + n);
+    c->em_frames_valid = false;
     if (!c->place) c->place.reset(new PlaceMeta());
     c->place->valid = false;
     c->place->rootVect = -1;

@@ -194,6 +194,10 @@ class TreeOps:
         from .tree_host import tree_log_likelihood
         return tree_log_likelihood(self.dev, self.tree)[0]
 
+    def expectationMaximizationCalculationRates(self, model="UNREST"):     # M:10077 (trackMutations=False)
+        from .tree_host import estimate_rates
+        return estimate_rates(self.dev, self.tree, model)
+
     def traverseTreeToOptimizeBranchLengths(self, effectivelyNon0BLen, fastPass=False):  # M:8727 (default: the Gauss-Seidel sweep)
         from .tree_host import optimize_branch_lengths, optimize_branch_lengths_fast_pass
         if fastPass:

@@ -26,6 +26,7 @@ EXPORTS = [
     "maple_minor_candset", "maple_placement_search_batch", "maple_placement_prepare", "maple_placement_ahead", "maple_placement_ahead_stats", "maple_set_fatal_policy",
     "maple_timing_read_kind", "maple_placement_supports_batch",
     "maple_candset_destroy", "maple_spr_search_visited", "maple_arena_compact", "maple_append_queries_argmax_dev", "maple_comm_unique_id", "maple_comm_init", "maple_argmax_allreduce_dev", "maple_tree_rebuild_lists",
+    "maple_em_expectation", "maple_em_rates",
 ]
 
 
@@ -58,6 +59,14 @@ class MaplePlacementParams(C.Structure):
     _fields_ = [("oneMutBLen", C.c_double), ("effectivelyNon0BLen", C.c_double), ("thresholdLogLK", C.c_double),
                 ("thresholdLogLKoptimization", C.c_double), ("thresholdLogLKconsecutivePlacement", C.c_double),
                 ("allowedFails", C.c_int32), ("strictStopRules", C.c_int32), ("onlyFindIdentical", C.c_int32)]
+
+
+class MapleEmTotals(C.Structure):
+    _fields_ = [("counts", C.c_double * 16), ("waitingTimes", C.c_double * 4), ("errorCount", C.c_double), ("totTreeLength", C.c_double),
+                ("observedTotNucsSites", C.c_int64), ("numTips", C.c_int64)]
+
+
+EM_MODELS = {"UNREST": 0, "GTR": 1}
 
 
 class MapleError(RuntimeError):
@@ -190,6 +199,7 @@ class Device:
         self._ck(self.lib.maple_set_model(self.h, _ptr(Qf), _ptr(sr), int(bool(usingErrorRate)),
                                           C.c_double(errorRateGlobal or 0.0), _ptr(er)))
         self.u = bool(usingErrorRate)
+        self.rv, self.ss = sr is not None, er is not None
 
     def get_model(self):
         cr = np.zeros(self.lRef + 1)
@@ -688,6 +698,34 @@ class Device:
                                                    _ptr(lower), _ptr(ur), _ptr(ul), _ptr(tu), C.c_double(bump_len), len(bad), _ptr(bad),
                                                    C.byref(nbad)))
         return lower, ur, ul, tu, np.unique(bad[: min(nbad.value, len(bad))])
+
+    def em_expectation(self, n_minor=None):
+        """The expectation part of one EM step on the uploaded tree (maple_em_expectation; the statistics of M:10113-10136 as
+        they stand at M:10852): a dict with counts [4][4], waitingTimes [4], errorCount, totTreeLength, observedTotNucsSites, numTips
+        and the per-site tables waitingTimesSites [lRef][4], countsSites, trackingNs, observedNucsSites, errorCountSites (zeros
+        where the current model has none).  n_minor[v] = len(minorSequences[v]), None = all 0."""
+        L = self.lRef
+        nm = None if n_minor is None else _i32(n_minor)
+        tot = MapleEmTotals()
+        wts, cs, tn, on, ecs = np.zeros(4 * L), np.zeros(L), np.zeros(L + 1), np.zeros(L + 1), np.zeros(L)
+        self._ck(self.lib.maple_em_expectation(self.h, _ptr(nm), C.byref(tot), _ptr(wts), _ptr(cs), _ptr(tn), _ptr(on), _ptr(ecs)))
+        return dict(counts=np.array(tot.counts).reshape(4, 4), waitingTimes=np.array(tot.waitingTimes), errorCount=tot.errorCount,
+                    totTreeLength=tot.totTreeLength, observedTotNucsSites=int(tot.observedTotNucsSites), numTips=int(tot.numTips),
+                    waitingTimesSites=wts.reshape(L, 4), countsSites=cs, trackingNs=tn, observedNucsSites=on, errorCountSites=ecs)
+
+    def em_rates(self, n_minor=None, model="UNREST"):
+        """One whole EM step on the uploaded tree (maple_em_rates, M:10077-10947): (Q [4][4], siteRates or None, errorRate or None,
+        siteErrRates or None) for the model of the last set_model.  model: "UNREST" / "GTR" (another name is an error unless the
+        current model has error rates, as at M:10877)."""
+        L = self.lRef
+        nm = None if n_minor is None else _i32(n_minor)
+        code = model if isinstance(model, int) else EM_MODELS.get(model, 2)
+        Q = np.zeros(16)
+        sr = np.zeros(L) if getattr(self, "rv", False) else None
+        se = np.zeros(L) if getattr(self, "ss", False) else None
+        er = C.c_double()
+        self._ck(self.lib.maple_em_rates(self.h, _ptr(nm), int(code), _ptr(Q), _ptr(sr), C.byref(er), _ptr(se)))
+        return Q.reshape(4, 4), sr, (er.value if self.u else None), se
 
     def timing_read(self):
         """(number of timed *_dev launches since the last reset, their summed HIP-event time in ms)."""

@@ -205,6 +205,15 @@ def compact_arena(dev: Device, tree: HostTree, keep=()):
     return remap(np.asarray(keep, dtype=np.int32)) if len(keep) else np.zeros(0, np.int32)
 
 
+def estimate_rates(dev: Device, tree: HostTree, model="UNREST"):
+    """expectationMaximizationCalculationRates(tree, root), M:10077-10947, for the uploaded ``tree`` and the model ``dev`` holds:
+    the reference's 4-tuple (mutMatrix as nested lists, siteRates, errorRate, siteErrRates; None where the model has none).
+    The walk over the branches runs on the GPU (maple_em_rates), the minor-sequence counts come from ``tree.n_minor``."""
+    Q, sr, er, se = dev.em_rates(tree.n_minor, model)
+    return ([[float(x) for x in row] for row in Q], None if sr is None else [float(x) for x in sr], er,
+            None if se is None else [float(x) for x in se])
+
+
 def tree_log_likelihood(dev: Device, tree: HostTree):
     """calculateTreeLikelihood (M:9721-9779) on the uploaded tree: one merge launch (returnLK) over every internal
     node's two stored lower lists, one findProbRoot launch, summed in the reference's post-order."""
