@@ -104,6 +104,15 @@ static int need_model(maple_ctx *c)
     return MAPLE_OK;
 }
 
+// An arena mark (maple_arena_mark) whose lists go on every path out of its scope: release() where the call is done with them
+// and their release may fail the call, the destructor on the paths that return before that.
+struct MarkGuard {
+    maple_ctx *c; int64_t mark = 0; bool on = false;
+    int take() { const int rc = maple_arena_mark(c, &mark); on = rc == MAPLE_OK; return rc; }
+    int release() { if (!on) return MAPLE_OK; on = false; return maple_arena_release(c, mark); }
+    ~MarkGuard() { if (on) (void)maple_arena_release(c, mark); }
+};
+
 
 // ---- defined in maple_hip.hip ---------------------------------------------------------------------------------------------
 // scratch lists into the arena, ids handed out (-1 for None): see the definition

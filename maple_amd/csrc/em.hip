@@ -150,11 +150,6 @@ std::vector<int2> pass_mutation_list(const std::vector<int2> &m1, const int32_t 
     return out;
 }
 
-struct MarkGuard {                     // the call's temporaries (the parent lists passed through reference branches) go on every path
-    maple_ctx *c; int64_t mark; bool on = false;
-    ~MarkGuard() { if (on) (void)maple_arena_release(c, mark); }
-};
-
 EmScratch &scratch(maple_ctx *c)
 {
     if (!c->em) { c->em.reset(new EmScratch()); c->em_frames_valid = false; }
@@ -260,9 +255,8 @@ int expectation(maple_ctx *c, const int32_t *nMinorArr, EmHost &H)
         }
     }
     const int32_t nB = (int32_t)node.size();
-    MarkGuard guard{c, 0};
-    TRY(maple_arena_mark(c, &guard.mark));
-    guard.on = true;
+    MarkGuard guard{c};                // the call's temporaries (the parent lists passed through reference branches) go on every path
+    TRY(guard.take());
     if (!passIdx.empty()) {                                              // M:10154-10155, all reference branches in one launch
         std::vector<uint8_t> down(passIdx.size(), 0);
         std::vector<int32_t> out(passIdx.size());

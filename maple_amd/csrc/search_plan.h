@@ -1,12 +1,14 @@
 // maple_amd/csrc/search_plan.h -- how large the pools of the two SPR tiers are, how many lanes, wavefronts and scratch slabs a
-// launch gets, and what is remembered for the next call: functions of numbers, nothing else.  No HIP, nothing of the project
-// (record sizes come in as fields, filled by the caller with sizeof), so it compiles and is tested on its own
-// (tests/search_plan_main.cpp, tests/test_search_plan.py).  frontier_search (frontier.hip) and run_queries (spr_batch.hip) fill
-// the input, reserve what the plan says and launch.
+// launch gets, what is remembered for the next call, and which search of a round goes to which tier: functions of numbers and
+// flags, nothing else.  No HIP, nothing of the project (record sizes come in as fields, filled by the caller with sizeof), so it
+// compiles and is tested on its own (tests/search_plan_main.cpp, tests/test_search_plan.py; the routing rules:
+// tests/search_route_main.cpp, tests/test_search_route.py).  frontier_search (frontier.hip), run_queries and
+// maple_spr_search_batch (spr_batch.hip) fill the input, reserve what the plan says and launch.
 #pragma once
 #include <algorithm>
 #include <cstddef>
 #include <cstdint>
+#include <vector>
 
 namespace maple {
 namespace plan {
@@ -308,6 +310,150 @@ static inline LanePlan plan_lane_launch(const LanePlanIn &in)
     }
     return p;
 }
+
+// ---- which search of a round goes where (maple_spr_search_batch, spr_batch.hip) -------------------------------------------
+
+// The tree was patched since its tables were built.  A small batch (the re-search of proposed moves before they are
+// applied) runs on the patched node records alone, through the frontier tier with no hand-over to the dense tier -- unless
+// one of its searches is a whole-tree search by construction (a zero-length branch without an error model); everything
+// else rebuilds the tables first.
+static inline bool patched_only(bool nodesCurrent, bool matTree, int n, int searchTier, bool tracing, bool wantsLists, int requested,
+                                bool usingErrorRate, bool anyZeroLength)
+{
+    if (!(nodesCurrent && !matTree && n <= 64 && searchTier == 0 && !tracing && !wantsLists)) return false;
+    return !(requested >= 0 && !usingErrorRate && anyZeroLength);
+}
+
+// A search that scores more branches than the budget is handed to the dense path, which costs it one appendProbNode per
+// branch of the tree -- so the budget that pays grows with the tree: 1/64 of the scored branches, measured best at 10 000
+// tips (256: 91 ms per round; 128: 100, 384: 97) and at 100 000 (2 048: 1.08 s; 256: 2.69, 1 024: 1.13, 4 096: 1.20)
+// (requested: the caller's wideSearchBudget -- 0: this rule, negative: no dense tier; budgetDefault: MAPLE_WIDE_BUDGET_DEFAULT)
+static inline int wide_budget(int requested, int nScored, bool usingErrorRate, bool patchedOnly, int budgetDefault)
+{
+    int wideBudget = requested == 0 ? std::max(budgetDefault, std::min(8192, nScored / 64)) : requested;
+    if (patchedOnly) wideBudget = -1;                                   // (no tree-sized table is current)
+    // (a long search costs the wave-assisted lane tier a tenth of what it cost one lane: twice the budget pays -- 100 000 tips:
+    // 2 132 / 3 072 / 4 096 / 6 144 -> 693 / 688 / 668 / 692 ms per round; 10 000 tips: 256 / 384 / 512 -> 75 / 72 / 72)
+    // (with an error model too, since the frontier tier: 100 000 tips, budget 2 132 / 3 000 / 4 264 / 8 528 -> 532 / 447 / 420 / 441 ms
+    // per round -- the searches between 2 000 and 4 000 items are the ones with the longest removed lists, which the dense kernel
+    // walks slowest: 28 116 rows take it 260 ms, 25 785 rows 114)
+    // (1 000 000 tips, 8 192 / 16 384: 2.32 / 2.73 s per 131 072 searches -- the pools of the longer searches are reallocated on
+    // the way: with an error model the doubling stops at 8 192)
+    if (requested == 0) wideBudget = usingErrorRate ? std::min(2 * wideBudget, std::max(wideBudget, 8192)) : 2 * wideBudget;
+    return wideBudget;                                                  // (> 0: searches over it go to the dense tier, "hybrid")
+}
+
+// An item of the frontier tier costs about what half a (search, branch) pair costs the dense tier on full walks (1.1e9
+// items/s against 2.3e9 pairs/s), so a search only pays for a row of the whole tree once it has expanded half a tree's
+// worth of items; the searches from zero-length branches (whole-tree searches without an error model) never start here.
+// (With an error model there are no searches known to be whole-tree ones beforehand, a fifth of all searches is long, and
+// half a tree's worth of items each does not fit any pool -- 5e8 items at 100 000 tips and counting: those searches
+// leave at the lane tiers' budget.)
+static inline int frontier_budget(int wideBudget, int requested, int nScored, bool usingErrorRate)
+{
+    if (wideBudget <= 0) return 0;
+    return usingErrorRate ? wideBudget : std::max(wideBudget, requested == 0 ? nScored / 2 : 0);
+}
+
+// rows the (query x node) score table may have: 4 GiB, more on big trees -- a row of a 1 000 000-tip tree is 16 MB and every
+// launch over the table wants thousands of searches (one per wavefront): up to half of what is free (plus what the table
+// already holds), 96 GiB at most.  Never below one row: a chunk of the dense tier is at least one search, and the rows made
+// ahead want 64 searches (pre_rows_fit), which neither 0 nor 1 row takes.
+static inline size_t score_rows_max(bool freeKnown, size_t freeBytes, size_t cacheCapBytes, int nNodes)
+{
+    size_t budget = (size_t)4ull << 30;
+    if (freeKnown) budget = std::max(budget, std::min((freeBytes + cacheCapBytes) / 2, (size_t)96ull << 30));
+    return std::max<size_t>(1, budget / ((size_t)nNodes * sizeof(double)));
+}
+
+// what the tuning and the state of the context say about a call's whole-tree searches
+struct RouteIn {
+    int wideBudget = 0;                // wide_budget()
+    bool usingErrorRate = false, matTree = false, useFrontier = false;
+    bool scanValid = false, havePlace = false;   // the clade-scan tables and the frames' tables exist
+    bool hintsCoverTree = false;       // the hints of the call before are as long as the tree
+    bool noCladeScan = false, denseWideScoring = false, wideOutsideFrontier = false, noOverHint = false;   // the tuning's
+};
+
+// Rows of the score table made ahead, on a side stream next to the budgeted pass: for the searches from zero-length branches
+// (no error model: the witness filter's) or for those that ran over the budget the last time (error model: the hinted ones)
+enum PreRowsKind { PRE_NONE = 0, PRE_WITNESS = 1, PRE_HINTED = 2 };
+static inline PreRowsKind pre_rows_kind(const RouteIn &r)
+{
+    const bool hybrid = r.wideBudget > 0;
+    if (hybrid && !r.usingErrorRate && r.wideBudget > 16
+        && (!r.matTree || (r.scanValid && r.havePlace && !r.noCladeScan && !r.denseWideScoring && !r.wideOutsideFrontier)))
+        return PRE_WITNESS;
+    if (hybrid && r.usingErrorRate && r.useFrontier && !r.noOverHint && r.hintsCoverTree && r.wideBudget > 16 && r.scanValid && r.havePlace
+        && !r.noCladeScan && !r.wideOutsideFrontier)
+        return PRE_HINTED;
+    return PRE_NONE;
+}
+// ... are made for 64 searches or more, as many as the table takes
+static inline bool pre_rows_fit(size_t nCand, size_t rowsMax) { return nCand >= 64 && nCand <= rowsMax; }
+// ... with rows to spare for searches that run over their budget unannounced (the witness filter's only)
+static inline int pre_rows_spare(size_t nCand, size_t rowsMax, bool witness) { return witness ? (int)std::min<size_t>(4096, rowsMax - nCand) : 0; }
+
+// Trees with local references: the rows of the searches that ran over their budget are made in the ROOT's frame as well
+// (appendProbNode does not depend on the frame) and replayed inside the frontier tier; only what the tier hands back goes the
+// frame-by-frame way.
+static inline bool root_rows_ok(const RouteIn &r, int nF, size_t nWide)
+{
+    return nF > 1 && r.useFrontier && r.scanValid && r.havePlace && !r.noCladeScan && !r.wideOutsideFrontier && nWide >= 64;
+}
+
+// The searches that left the budgeted pass (`wide`: positions in the batch) when rows were made ahead: `take` are replayed over
+// row `row` each -- their own (rowOf >= 0) or, for the unannounced ones, the next of the `spare` rows behind the mZ made ahead
+// (nSpare handed out) -- and `rest` go on to the dense tier's chunks.  (A tree with local references: what the tier did not finish
+// over these rows goes frame by frame -- the one-wavefront-per-search replay wants the removed list in every frame.)
+struct WideSplit { std::vector<int32_t> take, row, rest; int nSpare = 0; };
+static inline WideSplit split_wide(const std::vector<int32_t> &wide, const std::vector<int32_t> &rowOf, int mZ, int spare, bool matTree)
+{
+    WideSplit s;
+    for (int32_t i : wide) {
+        if (matTree) { s.rest.push_back(i); continue; }
+        if (rowOf[i] >= 0) { s.take.push_back(i); s.row.push_back(rowOf[i]); }
+        else if (s.nSpare < spare) { s.take.push_back(i); s.row.push_back(mZ + s.nSpare++); }
+        else s.rest.push_back(i);
+    }
+    return s;
+}
+
+// The frame-by-frame chunk: the removed list goes into EVERY reference frame, so the batch is bounded by what the arena can
+// take (a third of its free entries and aux values; nEnt, nAux: the removed lists of the m searches offered) and by 8 Mi
+// (query, frame) items.  laneOnly: too many frames for this arena (a 100 000-tip tree has ~2 000) -- batches this small would
+// turn the replay into a chain of one-lane launches, the remaining wide searches run lane-only instead.
+struct FrameChunk { int m; bool laneOnly; };
+static inline FrameChunk frame_chunk(int m, int nF, int64_t arenaFreeEnt, int64_t arenaFreeAux, const int32_t *nEnt, const int32_t *nAux)
+{
+    const int64_t freeEnt = arenaFreeEnt / 3, freeAux = arenaFreeAux / 3;
+    int64_t needEnt = 0, needAux = 0;
+    int k = 0;
+    for (; k < m; k++) {
+        needEnt += (int64_t)nF * (nEnt[k] + 24);
+        needAux += (int64_t)nF * (nAux[k] + 8);
+        if (needEnt > freeEnt || needAux > freeAux || (int64_t)(k + 1) * nF > (8ll << 20)) break;
+    }
+    return FrameChunk{k, k < m && k < 2048};
+}
+
+// the score table for a chunk of `need` scores: grow-only and at least doubling, up to a full chunk's rows
+static inline size_t cache_reserve(size_t need, size_t cap, size_t chunkRows, int nNodes)
+{
+    if (need > cap) need = std::min(std::max(need, 2 * cap), std::max(chunkRows * (size_t)nNodes, need));
+    return need;
+}
+
+// The routing hint of searches with an error model (the node's search ran over the budget the last time it was searched on
+// this tree).  Hints taken under another budget or threshold say nothing about this one: all are dropped
+static inline bool hints_stale(int hintBudget, double hintEff0, int wideBudget, double eff0) { return hintBudget != wideBudget || hintEff0 != eff0; }
+// a hinted search leaves the budgeted pass at once -- unless it has a row made ahead: a whole-tree search inside the pass
+static inline bool hint_sends_on(bool hinted, int row) { return hinted && !(row >= 0); }
+// what the pass saw: over the budget -> the hint is set (nAppend -1: left for shorten(), k_fr_begin -- not over the budget;
+// a search the hint sent on says nothing new)
+static inline bool hint_set(int status, int nAppend, bool sentOn) { return status == -5 && nAppend >= 0 && !sentOn; }
+// (a hinted search that turned out short -- the tree changed around it -- is tried within the budget again next time)
+static inline bool hint_clear(bool hinted, int status, int nAppend, int wideBudget) { return hinted && status == 0 && nAppend <= wideBudget / 4; }
 
 }  // namespace plan
 }  // namespace maple

@@ -18,7 +18,6 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
-#include <functional>
 #include <string>
 #include <vector>
 
@@ -1085,16 +1084,15 @@ extern "C" int maple_spr_search_batch(maple_ctx *c, int32_t n, const int32_t *no
     if (!c->tree_set) return fail(c, MAPLE_ERR_STATE, "maple_tree_upload has not been called");
     for (int i = 0; i < n; i++)
         if (nodes[i] < 0 || nodes[i] >= c->dtree.n) return fail(c, MAPLE_ERR_ARG, "nodes[%d] = %d is not a node", i, nodes[i]);
-    // The tree was patched since its tables were built.  A small batch (the re-search of proposed moves before they are
-    // applied) runs on the patched node records alone, through the frontier tier with no hand-over to the dense tier -- unless
-    // one of its searches is a whole-tree search by construction (a zero-length branch without an error model); everything
-    // else rebuilds the tables first.
+    // The tree was patched since its tables were built: a small batch runs on the patched node records alone
+    // (plan::patched_only), everything else rebuilds the tables first.
     bool patchedOnly = false;
     c->last_search_frontier_only = false;
     if (c->tree_stale) {
-        patchedOnly = c->nodes_current && !c->tree_has_mut && n <= 64 && sp->searchTier == 0 && c->trace_query < 0 && !outRprList;
-        for (int i = 0; i < n && patchedOnly; i++)
-            if (sp->wideSearchBudget >= 0 && !c->dm.usingErrorRate && c->h_tree_dist[nodes[i]] == 0.0) patchedOnly = false;
+        bool anyZeroLength = false;
+        for (int i = 0; i < n && !anyZeroLength; i++) anyZeroLength = c->h_tree_dist[nodes[i]] == 0.0;
+        patchedOnly = plan::patched_only(c->nodes_current, c->tree_has_mut, n, sp->searchTier, c->trace_query >= 0, outRprList != nullptr,
+                                         sp->wideSearchBudget, c->dm.usingErrorRate, anyZeroLength);
         if (!patchedOnly) TRY(tree_rebuild_from_host(c));
     }
     const bool dbgT = c->tuning.verbose != 0;
@@ -1145,9 +1143,10 @@ extern "C" int maple_spr_search_batch(maple_ctx *c, int32_t n, const int32_t *no
     const bool assistFew = !c->dm.usingErrorRate;      // few searching lanes per wavefront, every request served by all 64 lanes
     // (the frontier tier, frontier.hip / frontier_upd.hip; searchTier 1 keeps every search in the one-lane kernels)
     const bool useFrontier = sp->searchTier == 0 && c->trace_query < 0;
-    const std::vector<int32_t> *rowOverride = nullptr;                 // rows of the score table the next cached launch reads
-    FiniteRows finRows{nullptr, nullptr, 0};                           // ... and, where the rows come with one, the bitmap of their finite scores
+    const int nT = c->dtree.n;
     const int finWords = (c->n_scored + 63) / 64;                      // (words per row: one per tile of 64 candidates of the dense kernel)
+    // rows of the score table come with the bitmap of their finite scores where whoever made them says so
+    auto fin_rows = [&](bool fin) { return fin ? FiniteRows{c->s_fin_mask.p, c->s_fin_prefix.p, finWords} : FiniteRows{nullptr, nullptr, 0}; };
     auto fin_reserve = [&](size_t rows) -> int {
         HIPCK(c, c->s_fin_mask.reserve_exact(std::max(rows * (size_t)finWords, c->s_fin_mask.cap)));
         HIPCK(c, c->s_fin_prefix.reserve_exact(std::max(rows * (size_t)(finWords + 1), c->s_fin_prefix.cap)));
@@ -1156,12 +1155,53 @@ extern "C" int maple_spr_search_batch(maple_ctx *c, int32_t n, const int32_t *no
     auto fin_prefix = [&](hipStream_t st, size_t row0, size_t rows) -> int {   // (after the dense launch that wrote those rows' bitmaps)
         return launch_finite_prefix(c, st, rows, finWords, c->s_fin_mask.p + row0 * finWords, c->s_fin_prefix.p + row0 * (finWords + 1));
     };
-    std::function<int()> afterLaunch;                                  // called once, right after the next search kernel is queued
-    auto run_queries = [&](std::vector<int32_t> todo, std::vector<int32_t> slot, const double *cacheS, int budgetNow,
-                           const int32_t *rTable, int nF) -> int {
+    // Dense rows of the score table, row0 onwards, on stream st: the m searches ql / qt / qb (removed list, isRemovedTip, removedBLen: on
+    // the device; qBytes: what reading the lists once costs) against every scored candidate -- the tree's own lists or, on a tree with
+    // local references, their copies in the root's frame (ql in that frame too); with the rows' bitmaps where `fin` says so.
+    // nFchunk > 0: ql holds the list in each of nFchunk frames per search and the candidates go frame chunk by frame chunk.
+    auto dense_rows = [&](hipStream_t st, int m, const int32_t *ql, const uint8_t *qt, const double *qb, double qBytes, size_t row0, bool rootFrame,
+                          bool fin, int nFchunk = 0) -> int {
+        TRY(launch_append_queries(c, st, m, ql, c->n_scored, rootFrame ? c->s_cand_root.p : c->t_i32[8].p, 0, 0.0, c->s_cache.p + row0 * (size_t)nT, nT,
+                                  rootFrame ? c->t_cand_rank.p : c->t_scored_col.p, qt, qb, MAPLE_K_SPR_SCORE,
+                                  (double)m * c->scored_bytes_total + qBytes, nullptr, nullptr, nFchunk ? c->t_frame_chunks.p : nullptr,
+                                  nFchunk ? c->n_frame_chunks : 0, nFchunk ? nFchunk : 1, fin ? c->s_fin_mask.p + row0 * finWords : nullptr));
+        if (fin) TRY(fin_prefix(st, row0, (size_t)m));
+        return MAPLE_OK;
+    };
+    // The side-stream scoring of the rows made ahead (pre_rows, below), queued once: right behind the first lane launch that follows,
+    // or where a pass without one begins.  BEHIND the lane launch: a workgroup of the dense kernel wants most of a compute unit's
+    // LDS, so it starts where the lane searches have thinned out -- launched first it would hold them off instead (measured: no
+    // overlap)
+    struct { bool pending = false, witness = false, rootFrame = false, fin = false; int mZ = 0; double qBytes = 0.0; } side;
+    auto queue_side_once = [&]() -> int {
+        if (!side.pending) return MAPLE_OK;
+        side.pending = false;
+        const int mZ = side.mZ;
+        // (every one of these searches has removedBLen = 0 and there is no error model: only the pairs the witness
+        // filter cannot rule out are walked -- witness.hip)
+        if (side.witness && side.fin && !c->tuning.denseWideScoring) {
+            long long pairs = 0;
+            TRY(witness_score(c, c->stream2, mZ, c->z_ql.p, c->z_qt.p, c->z_qb.p, c->n_scored, side.rootFrame ? c->s_cand_root.p : c->t_i32[8].p,
+                              side.rootFrame ? c->t_cand_rank.p : c->t_scored_col.p,
+                              c->s_cache.p, nT, c->s_fin_mask.p, finWords,
+                              c->n_scored ? c->scored_bytes_total / c->n_scored : 0.0, side.qBytes, &pairs));
+            if (dbgT) fprintf(stderr, "[maple] witness filter: %lld of %lld (search, branch) pairs walked\n", pairs, (long long)mZ * c->n_scored);
+            TRY(fin_prefix(c->stream2, 0, (size_t)mZ));
+        } else   // (a tree with local references: candidates and removed lists both in the root's frame, as for the witness filter)
+            TRY(dense_rows(c->stream2, mZ, c->z_ql.p, c->z_qt.p, c->z_qb.p, side.qBytes, 0, side.rootFrame, side.fin));
+        HIPCK(c, hipEventRecord(c->ev_join, c->stream2));
+        return MAPLE_OK;
+    };
+    // what a cached launch of run_queries replays over: the score table, the row of each query in it (null: query k has row k), the
+    // bitmap of the rows' finite scores where they come with one and, frame by frame, the removed lists' table (rTable, nF frames)
+    struct ReplayRows { const double *scores = nullptr; const std::vector<int32_t> *rowOf = nullptr; FiniteRows fin{nullptr, nullptr, 0};
+                        const int32_t *rTable = nullptr; int nF = 0; };
+    const ReplayRows noRows{};                                         // (a launch that scores for itself)
+    auto run_queries = [&](std::vector<int32_t> todo, std::vector<int32_t> slot, const ReplayRows &over, int budgetNow) -> int {
+        const double *cacheS = over.scores;
         int capW = plan::lane_start_cap_w(capW0, cacheS != nullptr, heavyQueries);
         std::vector<int32_t> rows(todo.size());                        // row of each query in the cache / frame tables
-        for (size_t k = 0; k < rows.size(); k++) rows[k] = rowOverride ? (*rowOverride)[k] : (int32_t)k;
+        for (size_t k = 0; k < rows.size(); k++) rows[k] = over.rowOf ? (*over.rowOf)[k] : (int32_t)k;
         if ((int)c->h_depth.size() >= c->dtree.n) {
             // Lanes pull searches from a counter, so a launch ends one search after the last one is pulled: the expensive
             // searches go first.  The expensive ones are those near the root (long lists: an updating step there merges
@@ -1252,20 +1292,16 @@ extern "C" int maple_spr_search_batch(maple_ctx *c, int32_t n, const int32_t *no
                                                                          poolA, poolUsed, poolCapW, poolCapA,                      \
                                                                          attempt == 0 ? c->trace_query : -1, c->s_trace_i.p,       \
                                                                          c->s_trace_d.p, 4096, c->s_trace_i.p ? c->s_trace_i.p + 4 * 4096 : nullptr, \
-                                                                         launchLanes, cacheS, budgetNow, rTable, nF,               \
+                                                                         launchLanes, cacheS, budgetNow, over.rTable, over.nF,     \
                                                                          cacheS ? c->s_i32[1].p : nullptr,                          \
                                                                          assistOK ? 1 + coopMaxHost : 0, (unsigned long long *)(c->s_counter.p + 6),          \
-                                                                         ovfChunks ? c->s_search_ws_big.p : nullptr, ovfChunks, cacheS ? finRows : FiniteRows{nullptr, nullptr, 0})
+                                                                         ovfChunks ? c->s_search_ws_big.p : nullptr, ovfChunks, over.fin)
             if (!cacheS && assistOK) DISPATCH3(c, k_spr_search_assisted, MAPLE_SPR_LAUNCH_ARGS);
             else DISPATCH3(c, k_spr_search, MAPLE_SPR_LAUNCH_ARGS);
 #undef MAPLE_SPR_LAUNCH_ARGS
             HIPCK(c, hipGetLastError());
             HIPCK(c, hipEventRecord(e1, c->stream));
-            if (afterLaunch) {                                             // (work for the side stream, queued behind this launch)
-                std::function<int()> f;
-                f.swap(afterLaunch);
-                TRY(f());
-            }
+            TRY(queue_side_once());                                        // (work for the side stream, queued behind this launch)
             std::vector<SearchOut> part(m);
             HIPCK(c, hipMemcpyAsync(part.data(), dout, (size_t)m * sizeof(SearchOut), hipMemcpyDeviceToHost, c->stream));
             HIPCK(c, hipStreamSynchronize(c->stream));
@@ -1303,23 +1339,12 @@ extern "C" int maple_spr_search_batch(maple_ctx *c, int32_t n, const int32_t *no
     // branch is a pure function of (query, branch), so those queries are scored against every branch by the batch
     // kernel (k_append_queries) and the state machine then only replays the traversal over the cached scores.
     // With MAT local references the removed list is first expressed in every reference frame (below).
-    // A search that scores more branches than the budget is handed to the dense path, which costs it one appendProbNode per
-    // branch of the tree -- so the budget that pays grows with the tree: 1/64 of the scored branches, measured best at 10 000
-    // tips (256: 91 ms per round; 128: 100, 384: 97) and at 100 000 (2 048: 1.08 s; 256: 2.69, 1 024: 1.13, 4 096: 1.20)
-    int wideBudget = sp->wideSearchBudget == 0 ? std::max(MAPLE_WIDE_BUDGET_DEFAULT, std::min(8192, c->n_scored / 64))
-                                               : sp->wideSearchBudget;
-    if (patchedOnly) wideBudget = -1;                                   // (no tree-sized table is current)
-    // (a long search costs the wave-assisted lane tier a tenth of what it cost one lane: twice the budget pays -- 100 000 tips:
-    // 2 132 / 3 072 / 4 096 / 6 144 -> 693 / 688 / 668 / 692 ms per round; 10 000 tips: 256 / 384 / 512 -> 75 / 72 / 72)
-    // (with an error model too, since the frontier tier: 100 000 tips, budget 2 132 / 3 000 / 4 264 / 8 528 -> 532 / 447 / 420 / 441 ms
-    // per round -- the searches between 2 000 and 4 000 items are the ones with the longest removed lists, which the dense kernel
-    // walks slowest: 28 116 rows take it 260 ms, 25 785 rows 114)
-    // (1 000 000 tips, 8 192 / 16 384: 2.32 / 2.73 s per 131 072 searches -- the pools of the longer searches are reallocated on
-    // the way: with an error model the doubling stops at 8 192)
-    if (sp->wideSearchBudget == 0) wideBudget = c->dm.usingErrorRate ? std::min(2 * wideBudget, std::max(wideBudget, 8192)) : 2 * wideBudget;
+    // A search that scores more branches than the budget is handed to the dense path (plan::wide_budget, search_plan.h, as are
+    // the other rules that say which search goes where).
+    const int wideBudget = plan::wide_budget(sp->wideSearchBudget, c->n_scored, c->dm.usingErrorRate, patchedOnly, MAPLE_WIDE_BUDGET_DEFAULT);
     const bool hybrid = wideBudget > 0;
-    if (c->over_hint_budget != wideBudget || c->over_hint_eff0 != sp->effectivelyNon0BLen) {   // (hints taken under another budget or
-        c->h_over_hint.clear();                                                                // threshold say nothing about this one)
+    if (plan::hints_stale(c->over_hint_budget, c->over_hint_eff0, wideBudget, sp->effectivelyNon0BLen)) {
+        c->h_over_hint.clear();
         c->over_hint_budget = wideBudget; c->over_hint_eff0 = sp->effectivelyNon0BLen;
     }
     if (hybrid && !(c->scan_valid && c->scan_eff == P.effNon0) && !c->tuning.noCladeScan) {
@@ -1327,8 +1352,12 @@ extern "C" int maple_spr_search_batch(maple_ctx *c, int32_t n, const int32_t *no
         if (dbgT) fprintf(stderr, "[maple] t=%.1f ms: scan tables of the tree built (first search since it changed)\n", tms(tStart, tnow()));
     }
     // rows of the score table come with the bitmap of their finite scores (FiniteRows) when the tables that go with it exist
-    bool useFin = hybrid && c->scan_valid && !c->tree_has_mut;         // (trees with local references: only for the rows of the searches
-                                                                       // known beforehand, below)
+    const bool finPlain = hybrid && c->scan_valid && !c->tree_has_mut; // (trees with local references: the rows made in the root's frame, below)
+    plan::RouteIn route;
+    route.wideBudget = wideBudget; route.usingErrorRate = c->dm.usingErrorRate; route.matTree = c->tree_has_mut; route.useFrontier = useFrontier;
+    route.scanValid = c->scan_valid; route.havePlace = c->place != nullptr; route.hintsCoverTree = (int)c->h_over_hint.size() >= c->dtree.n;
+    route.noCladeScan = c->tuning.noCladeScan != 0; route.denseWideScoring = c->tuning.denseWideScoring != 0;
+    route.wideOutsideFrontier = c->tuning.wideOutsideFrontier != 0; route.noOverHint = c->tuning.noOverHint != 0;
     // Without an error model the whole-tree searches are known before anything runs: they are the ones that start from a
     // zero-length branch (the routing hint in the kernel gives those 16 placements and sends them on).  Their dense scoring
     // needs nothing from the lane searches, so it is launched first, on a side stream, and shares the GPU with them -- the
@@ -1336,30 +1365,28 @@ extern "C" int maple_spr_search_batch(maple_ctx *c, int32_t n, const int32_t *no
     // searches in order, then up to `preSpare` searches that run over their budget unannounced.
     std::vector<int32_t> preIdx, preRowOf;
     int preSpare = 0;
-    const int nTpre = c->dtree.n;
+    bool preFin = false;                                               // (these rows come with their bitmaps)
     // Trees with MAT local references: appendProbNode does not depend on the frame its two lists are written in (the same sites
     // need work, with the same nucleotides, lengths and rates, in the same order), so the rows of these searches are made in the
     // ROOT's frame: every candidate list and every removed list re-expressed there once per call (passGenomeListThroughBranch up
     // the chain of frames), the witness filter and the pair walks as on a plain tree.
     const bool matPre = c->tree_has_mut;
-    int64_t preMark = -1;                                              // (the re-expressed lists live until the results are in)
+    MarkGuard preMark{c};                                              // (the re-expressed lists live until the results are in)
     std::vector<int32_t> preFrameParent, preFrameNode;
-    auto pre_rows_max = [&]() -> size_t {                             // rows the score table may have: half of what is free, 96 GiB at most
+    auto score_rows_max = [&]() -> size_t {                            // rows the score table may have, by what is free right now
         size_t freeB = 0, totalB = 0;
-        size_t budgetB = (size_t)4ull << 30;
-        if (hipMemGetInfo(&freeB, &totalB) == hipSuccess)
-            budgetB = std::max(budgetB, std::min((freeB + c->s_cache.cap * sizeof(double)) / 2, (size_t)96ull << 30));
-        return budgetB / ((size_t)nTpre * sizeof(double));
+        const bool freeKnown = hipMemGetInfo(&freeB, &totalB) == hipSuccess;
+        return plan::score_rows_max(freeKnown, freeB, c->s_cache.cap * sizeof(double), nT);
     };
     // the searches `preIdx` get their rows of the score table on the side stream, next to the pass that follows, and are whole-tree
     // searches inside the tier (witnessOK: removedBLen = 0 and no error model -- the witness filter instead of the dense kernel)
     auto pre_rows = [&](const bool witnessOK) -> int {
-        const size_t rowsMax = pre_rows_max();
-        if (preIdx.size() < 64 || preIdx.size() > rowsMax) preIdx.clear();
+        const size_t rowsMax = score_rows_max();
+        if (!plan::pre_rows_fit(preIdx.size(), rowsMax)) preIdx.clear();
         else {
-            preSpare = witnessOK ? (int)std::min<size_t>(4096, rowsMax - preIdx.size()) : 0;
+            preSpare = plan::pre_rows_spare(preIdx.size(), rowsMax, witnessOK);
             const int mZ = (int)preIdx.size();
-            HIPCK(c, c->s_cache.reserve_exact((size_t)(mZ + preSpare) * nTpre));
+            HIPCK(c, c->s_cache.reserve_exact((size_t)(mZ + preSpare) * nT));
             TRY(fin_reserve((size_t)mZ + preSpare));
             if (!c->stream2) {
                 HIPCK(c, c->stream2.create());
@@ -1384,15 +1411,15 @@ extern "C" int maple_spr_search_batch(maple_ctx *c, int32_t n, const int32_t *no
                 const PlaceMeta &Fm = *c->place;
                 // (the candidates' copies are made once per tree; the removed lists' copies live for this call)
                 TRY(ensure_cand_root(c));
-                TRY(maple_arena_mark(c, &preMark));
+                TRY(preMark.take());
                 std::vector<int32_t> qf(mZ);
                 for (int k = 0; k < mZ; k++) qf[k] = Fm.frameOf[nodes[preIdx[k]]];
                 TRY(lists_to_root_frame(c, ql, qf));
                 if (dbgT) fprintf(stderr, "[maple] t=%.1f ms: their removed lists in the root's frame\n", tms(tStart, tnow()));
                 preFrameParent = Fm.frameParent;
                 preFrameNode = Fm.frameNode;
-                useFin = true;
             }
+            preFin = finPlain || matPre;
             HIPCK(c, c->z_ql.reserve(mZ)); HIPCK(c, c->z_qt.reserve(mZ)); HIPCK(c, c->z_qb.reserve(mZ));
             HIPCK(c, hipEventRecord(c->ev_fork, c->stream));               // (everything the tree tables wait for)
             HIPCK(c, hipStreamWaitEvent(c->stream2, c->ev_fork, 0));
@@ -1400,36 +1427,14 @@ extern "C" int maple_spr_search_batch(maple_ctx *c, int32_t n, const int32_t *no
             HIPCK(c, hipMemcpyAsync(c->z_qt.p, qt.data(), (size_t)mZ, hipMemcpyHostToDevice, c->stream2));
             HIPCK(c, hipMemcpyAsync(c->z_qb.p, qb.data(), (size_t)mZ * sizeof(double), hipMemcpyHostToDevice, c->stream2));
             HIPCK(c, hipStreamSynchronize(c->stream2));                     // (the three vectors are locals)
-            // queued BEHIND the lane launch: a workgroup of the dense kernel wants most of a compute unit's LDS, so it starts
-            // where the lane searches have thinned out -- launched first it would hold them off instead (measured: no overlap)
-            afterLaunch = [c, mZ, nTpre, qBytes, fin_prefix, useFin, finWords, dbgT, matPre, witnessOK]() -> int {
-                // (every one of these searches has removedBLen = 0 and there is no error model: only the pairs the witness
-                // filter cannot rule out are walked -- witness.hip)
-                if (witnessOK && useFin && !c->tuning.denseWideScoring) {
-                    long long pairs = 0;
-                    TRY(witness_score(c, c->stream2, mZ, c->z_ql.p, c->z_qt.p, c->z_qb.p, c->n_scored, matPre ? c->s_cand_root.p : c->t_i32[8].p,
-                                      matPre ? c->t_cand_rank.p : c->t_scored_col.p,
-                                      c->s_cache.p, nTpre, c->s_fin_mask.p, finWords,
-                                      c->n_scored ? c->scored_bytes_total / c->n_scored : 0.0, qBytes, &pairs));
-                    if (dbgT) fprintf(stderr, "[maple] witness filter: %lld of %lld (search, branch) pairs walked\n", pairs, (long long)mZ * c->n_scored);
-                    TRY(fin_prefix(c->stream2, 0, (size_t)mZ));
-                    HIPCK(c, hipEventRecord(c->ev_join, c->stream2));
-                    return MAPLE_OK;
-                }
-                // (a tree with local references: candidates and removed lists both in the root's frame, as for the witness filter)
-                TRY(launch_append_queries(c, c->stream2, mZ, c->z_ql.p, c->n_scored, matPre ? c->s_cand_root.p : c->t_i32[8].p, 0, 0.0, c->s_cache.p, nTpre,
-                                          matPre ? c->t_cand_rank.p : c->t_scored_col.p, c->z_qt.p, c->z_qb.p, MAPLE_K_SPR_SCORE,
-                                          (double)mZ * c->scored_bytes_total + qBytes, nullptr, nullptr, nullptr, 0, 1, useFin ? c->s_fin_mask.p : nullptr));
-                if (useFin) TRY(fin_prefix(c->stream2, 0, (size_t)mZ));
-                HIPCK(c, hipEventRecord(c->ev_join, c->stream2));
-                return MAPLE_OK;
-            };
+            side.pending = true; side.witness = witnessOK; side.rootFrame = matPre; side.fin = preFin; side.mZ = mZ; side.qBytes = qBytes;
             if (dbgT) fprintf(stderr, "[maple] t=%.1f ms: %d searches %s to be scored on the side stream\n", tms(tStart, tnow()), mZ,
                               witnessOK ? "from zero-length branches" : "that ran over the budget the last time");
         }
         return MAPLE_OK;
     };
-    if (hybrid && !c->dm.usingErrorRate && wideBudget > 16 && (!matPre || (c->scan_valid && c->place && !c->tuning.noCladeScan && !c->tuning.denseWideScoring && !c->tuning.wideOutsideFrontier))) {
+    const plan::PreRowsKind preKind = plan::pre_rows_kind(route);
+    if (preKind == plan::PRE_WITNESS) {
         {   // a node on a zero-length branch is searched at all only if its current placement is bad enough (M:9674): the
             // kernel's own test, on the same appendProbNode, for all of them at once
             std::vector<int32_t> zi, pl, cl;
@@ -1451,13 +1456,12 @@ extern "C" int maple_spr_search_batch(maple_ctx *c, int32_t n, const int32_t *no
             if (dbgT) fprintf(stderr, "[maple] t=%.1f ms: current placements of %zu nodes on zero-length branches scored\n", tms(tStart, tnow()), zi.size());
         }
         TRY(pre_rows(true));
-    } else if (hybrid && c->dm.usingErrorRate && useFrontier && !c->tuning.noOverHint && (int)c->h_over_hint.size() >= c->dtree.n && wideBudget > 16
-               && c->scan_valid && c->place && !c->tuning.noCladeScan && !c->tuning.wideOutsideFrontier) {
+    } else if (preKind == plan::PRE_HINTED) {
         // With an error model nothing about a node says that its search will be long -- except that it was, the last time the node was
         // searched on this tree (h_over_hint, below).  Those searches get their rows now, on the side stream next to the budgeted
         // pass, and stay in the tier as whole-tree searches like the zero-length ones above: no budget's worth of items expanded for
         // nothing, no second pass over the tier for them.  (As many as the table takes; the rest leave the pass at once.)
-        const size_t rowsMax = pre_rows_max();
+        const size_t rowsMax = score_rows_max();
         for (int i = 0; i < n && preIdx.size() < rowsMax; i++)
             if (c->h_over_hint[nodes[i]] && !(matPre && c->h_tree_mut[nodes[i]] >= 0)) preIdx.push_back(i);   // (a reference node itself: as above)
         TRY(pre_rows(false));
@@ -1467,23 +1471,16 @@ extern "C" int maple_spr_search_batch(maple_ctx *c, int32_t n, const int32_t *no
     // removed list in place, touches the root while still updating lists, or overflows a pool) runs one lane per search.
     if (useFrontier) {
         if (dbgT) fprintf(stderr, "[maple] t=%.1f ms: prologue done\n", tms(tStart, tnow()));
-        if (afterLaunch) { std::function<int()> f; f.swap(afterLaunch); TRY(f()); }   // (the side-stream scoring starts alongside)
+        TRY(queue_side_once());                                        // (the side-stream scoring starts alongside)
         if (dbgT) fprintf(stderr, "[maple] t=%.1f ms: side-stream scoring queued\n", tms(tStart, tnow()));
         FrontierStats fs;
-        // An item of the frontier tier costs about what half a (search, branch) pair costs the dense tier on full walks (1.1e9
-        // items/s against 2.3e9 pairs/s), so a search only pays for a row of the whole tree once it has expanded half a tree's
-        // worth of items; the searches from zero-length branches (whole-tree searches without an error model) never start here.
-        // (With an error model there are no searches known to be whole-tree ones beforehand, a fifth of all searches is long, and
-        // half a tree's worth of items each does not fit any pool -- 5e8 items at 100 000 tips and counting: those searches
-        // leave at the lane tiers' budget.)
-        const int frontierBudget = !hybrid ? 0 : (c->dm.usingErrorRate ? wideBudget
-                                                                       : std::max(wideBudget, sp->wideSearchBudget == 0 ? c->n_scored / 2 : 0));
+        const int frontierBudget = plan::frontier_budget(wideBudget, sp->wideSearchBudget, c->n_scored, c->dm.usingErrorRate);
         // the searches scored on the side stream stay in the tier: their updating steps run with everybody else's, their clades
         // in the cached regime are scanned over the rows (k_fr_replay_wide)
         FrontierWide fw{nullptr, nullptr, FiniteRows{nullptr, nullptr, 0}, nullptr, 0};
         if (!preIdx.empty() && !c->tuning.wideOutsideFrontier) {
             fw.rowOf = preRowOf.data(); fw.cacheS = c->s_cache.p; fw.rowsReady = c->ev_join;
-            if (useFin) fw.fin = FiniteRows{c->s_fin_mask.p, c->s_fin_prefix.p, finWords};
+            fw.fin = fin_rows(preFin);
             if (matPre) {                                               // the frames' nesting, for the clade scans' short lists
                 TRY(h2d(c, c->s_frame_parent, preFrameParent.data(), preFrameParent.size()));
                 TRY(h2d(c, c->s_frame_node, preFrameNode.data(), preFrameNode.size()));
@@ -1495,13 +1492,13 @@ extern "C" int maple_spr_search_batch(maple_ctx *c, int32_t n, const int32_t *no
         // the node's search ran over the budget the last time it was searched on this tree (rounds repeat over the same nodes;
         // maple_tree_patch keeps node ids).  Such a search leaves at once.  Only a hint: the dense tier is exact for any search.
         std::vector<uint8_t> overHint;
-        if (hybrid && c->dm.usingErrorRate && !c->tuning.noOverHint && (int)c->h_over_hint.size() >= c->dtree.n) {
+        if (hybrid && route.usingErrorRate && !route.noOverHint && route.hintsCoverTree) {
             overHint.resize((size_t)n);
             size_t nHint = 0;
             hintedNow.assign((size_t)n, 0);
             for (int i = 0; i < n; i++) {
                 hintedNow[i] = c->h_over_hint[todo[i]];
-                overHint[i] = hintedNow[i] && !(!preRowOf.empty() && preRowOf[i] >= 0);   // (with a row: a whole-tree search inside this pass)
+                overHint[i] = plan::hint_sends_on(hintedNow[i] != 0, preRowOf.empty() ? -1 : preRowOf[i]);
                 nHint += overHint[i];
             }
             if (!nHint) overHint.clear();
@@ -1514,7 +1511,7 @@ extern "C" int maple_spr_search_batch(maple_ctx *c, int32_t n, const int32_t *no
             // what this pass saw: over the budget -> the hint is set; a hinted search's hint is looked at again when its result is in
             if ((int)c->h_over_hint.size() < c->dtree.n) c->h_over_hint.resize((size_t)c->dtree.n, 0);
             for (int i = 0; i < n; i++)
-                if (ho[i].status == -5 && ho[i].nAppend >= 0 && (overHint.empty() || !overHint[i])) c->h_over_hint[todo[i]] = 1;   // (nAppend -1: left for shorten(), k_fr_begin -- not over the budget)
+                if (plan::hint_set(ho[i].status, ho[i].nAppend, !overHint.empty() && overHint[i])) c->h_over_hint[todo[i]] = 1;
         }
         std::vector<int32_t> todoFb, slotFb;
         for (int i = 0; i < n; i++)
@@ -1525,9 +1522,9 @@ extern "C" int maple_spr_search_batch(maple_ctx *c, int32_t n, const int32_t *no
                     fs.itemsUpdating, fs.itemsCached, fs.tempLists, fs.tempWords, fs.tempAux, fs.records, todoFb.size(),
                     fs.overflow ? " (a pool overflowed)" : "");
         c->last_search_frontier_only = todoFb.empty() && !hybrid;
-        if (!todoFb.empty()) TRY(run_queries(todoFb, slotFb, nullptr, hybrid ? wideBudget : 0, nullptr, 0));
+        if (!todoFb.empty()) TRY(run_queries(todoFb, slotFb, noRows, hybrid ? wideBudget : 0));
     } else
-        TRY(run_queries(todo, slot, nullptr, hybrid ? wideBudget : 0, nullptr, 0));
+        TRY(run_queries(todo, slot, noRows, hybrid ? wideBudget : 0));
     if (dbgT) fprintf(stderr, "[maple] t=%.1f ms: budgeted pass done\n", tms(tStart, tnow()));
     if (hybrid) {
         std::vector<int32_t> wide;
@@ -1536,92 +1533,59 @@ extern "C" int maple_spr_search_batch(maple_ctx *c, int32_t n, const int32_t *no
         if (!preIdx.empty()) {
             // replay what was scored on the side, together with as many unannounced ones as the spare rows take
             const int mZ = (int)preIdx.size();
-            std::vector<int32_t> qn, sl, rowsNow, rest, ql2;
+            plan::WideSplit ws = plan::split_wide(wide, preRowOf, mZ, preSpare, matPre);
+            std::vector<int32_t> qn, ql2;
             std::vector<uint8_t> qt2;
             std::vector<double> qb2;
-            for (int32_t i : wide) {
-                const int node = nodes[i];
-                // (a tree with local references: what the tier did not finish over these rows goes frame by frame, below -- the
-                // one-wavefront-per-search replay wants the removed list in every frame)
-                if (matPre) { rest.push_back(i); continue; }
-                if (preRowOf[i] >= 0) { qn.push_back(node); sl.push_back(i); rowsNow.push_back(preRowOf[i]); }
-                else if ((int)ql2.size() < preSpare) {
-                    qn.push_back(node); sl.push_back(i); rowsNow.push_back(mZ + (int)ql2.size());
-                    ql2.push_back(c->h_tree_lower[node]); qt2.push_back(c->h_tree_tip[node]); qb2.push_back(c->h_tree_dist[node]);
-                } else rest.push_back(i);
+            for (size_t k = 0; k < ws.take.size(); k++) {
+                const int node = nodes[ws.take[k]];
+                qn.push_back(node);
+                if (ws.row[k] >= mZ) { ql2.push_back(c->h_tree_lower[node]); qt2.push_back(c->h_tree_tip[node]); qb2.push_back(c->h_tree_dist[node]); }
             }
-            if (!ql2.empty()) {
+            if (!ql2.empty()) {                                         // (the spare rows, in order, behind the mZ made ahead)
                 const int m2 = (int)ql2.size();
                 TRY(h2d(c, c->s_i32[6], ql2.data(), (size_t)m2));
                 TRY(h2d(c, c->s_u8[3], qt2.data(), (size_t)m2));
                 TRY(h2d(c, c->s_f64[3], qb2.data(), (size_t)m2));
                 double qBytes = 0.0;
                 for (int k = 0; k < m2; k++) qBytes += 8.0 * c->h_n_ent[ql2[k]] + 8.0 * c->h_n_aux[ql2[k]];
-                TRY(launch_append_queries(c, c->stream, m2, c->s_i32[6].p, c->n_scored, c->t_i32[8].p, 0, 0.0,
-                                          c->s_cache.p + (size_t)mZ * nTpre, nTpre, c->t_scored_col.p, c->s_u8[3].p, c->s_f64[3].p,
-                                          MAPLE_K_SPR_SCORE, (double)m2 * c->scored_bytes_total + qBytes, nullptr, nullptr, nullptr, 0, 1,
-                                          useFin ? c->s_fin_mask.p + (size_t)mZ * finWords : nullptr));
-                if (useFin) TRY(fin_prefix(c->stream, (size_t)mZ, (size_t)m2));
+                TRY(dense_rows(c->stream, m2, c->s_i32[6].p, c->s_u8[3].p, c->s_f64[3].p, qBytes, (size_t)mZ, false, preFin));
             }
-            if (afterLaunch) { std::function<int()> f; f.swap(afterLaunch); TRY(f()); }   // (no lane launch took it)
+            TRY(queue_side_once());                                     // (no lane launch took it)
             HIPCK(c, hipStreamWaitEvent(c->stream, c->ev_join, 0));
-            if (!qn.empty()) {
-                rowOverride = &rowsNow;
-                if (useFin) finRows = FiniteRows{c->s_fin_mask.p, c->s_fin_prefix.p, finWords};
-                const int rc = run_queries(qn, sl, c->s_cache.p, 0, nullptr, 0);
-                finRows = FiniteRows{nullptr, nullptr, 0};
-                rowOverride = nullptr;
-                if (rc != MAPLE_OK) return rc;
-            }
-            if (dbgT) fprintf(stderr, "[maple] t=%.1f ms: %zu pre-scored and %zu other wide searches replayed, %zu left\n", tms(tStart, tnow()), qn.size() - ql2.size(), ql2.size(), rest.size());
-            wide.swap(rest);
+            if (!qn.empty()) TRY(run_queries(qn, ws.take, ReplayRows{c->s_cache.p, &ws.row, fin_rows(preFin)}, 0));
+            if (dbgT) fprintf(stderr, "[maple] t=%.1f ms: %zu pre-scored and %zu other wide searches replayed, %zu left\n", tms(tStart, tnow()), qn.size() - ql2.size(), ql2.size(), ws.rest.size());
+            wide.swap(ws.rest);
         }
         const PlaceMeta &F = *c->place;
-        const int nT = c->dtree.n, nF = c->tree_has_mut ? F.nF : 1;
-        const size_t rowBytes = (size_t)nT * sizeof(double);
-        size_t cacheBudget = (size_t)4ull << 30;                      // (query x node) score table: 4 GiB, more on big trees
-        {   // a row of a 1 000 000-tip tree is 16 MB and every launch over the table wants thousands of searches (one per
-            // wavefront): up to half of what is free, 96 GiB at most
-            size_t freeB = 0, totalB = 0;
-            if (hipMemGetInfo(&freeB, &totalB) == hipSuccess) {
-                const size_t half = (freeB + c->s_cache.cap * sizeof(double)) / 2;
-                cacheBudget = std::max(cacheBudget, std::min(half, (size_t)96ull << 30));
-            }
-        }
-        size_t chunk = cacheBudget / rowBytes;
-        if (chunk < 1) chunk = 1;
-        // Trees with local references: the rows of the searches that ran over their budget are made in the ROOT's frame as well
-        // (appendProbNode does not depend on the frame, see above) and replayed inside the frontier tier; only what the tier hands
-        // back goes the frame-by-frame way.
-        const bool rootRowsOK = nF > 1 && useFrontier && c->scan_valid && c->place && !c->tuning.noCladeScan && !c->tuning.wideOutsideFrontier
-                                && wide.size() >= 64;
+        const int nF = c->tree_has_mut ? F.nF : 1;
+        const size_t chunk = score_rows_max();                        // (searches of a launch over the score table)
+        // Trees with local references: rows in the ROOT's frame here as well, where plan::root_rows_ok says so
+        const bool rootRowsOK = plan::root_rows_ok(route, nF, wide.size());
         std::vector<int32_t> frameWay;                                  // (searches of a tree with references left to the old path)
         for (int wpass = 0; wpass < 2; wpass++) {
         if (wpass == 1) { if (frameWay.empty()) break; wide.swap(frameWay); frameWay.clear(); }
         const bool rootRows = rootRowsOK && wpass == 0;
+        // (a tree whose reference nodes the root does not reach has one frame: its rows come with the bitmap once those made ahead did)
+        const bool chunkFin = finPlain || rootRows || preFin;
         size_t w0 = 0;
         while (w0 < wide.size()) {
             int m = (int)std::min(chunk, wide.size() - w0);
             if (nF > 1 && !rootRows) {
-                // the removed list goes into EVERY reference frame: bound the batch by what the arena can take
-                const int64_t freeEnt = (c->cap_ent - c->used_ent) / 3, freeAux = (c->cap_aux - c->used_aux) / 3;
-                int64_t needEnt = 0, needAux = 0;
-                int k = 0;
-                for (; k < m; k++) {
+                // the removed list goes into EVERY reference frame: plan::frame_chunk bounds the batch by what the arena can take
+                std::vector<int32_t> nEnt(m), nAux(m);
+                for (int k = 0; k < m; k++) {
                     const int32_t l = c->h_tree_lower[nodes[wide[w0 + k]]];
-                    needEnt += (int64_t)nF * (c->h_n_ent[l] + 24);
-                    needAux += (int64_t)nF * (c->h_n_aux[l] + 8);
-                    if (needEnt > freeEnt || needAux > freeAux || (int64_t)(k + 1) * nF > (8ll << 20)) break;
+                    nEnt[k] = l >= 0 ? c->h_n_ent[l] : 0; nAux[k] = l >= 0 ? c->h_n_aux[l] : 0;
                 }
-                if (k < m && k < 2048) {
-                    // Too many frames for this arena (a 100 000-tip tree has ~2 000): batches this small would turn the
-                    // replay into a chain of one-lane launches.  The remaining wide searches run lane-only instead.
+                const plan::FrameChunk fc = plan::frame_chunk(m, nF, c->cap_ent - c->used_ent, c->cap_aux - c->used_aux, nEnt.data(), nAux.data());
+                if (fc.laneOnly) {
                     std::vector<int32_t> rest, restSlot;
                     for (size_t w = w0; w < wide.size(); w++) { rest.push_back(nodes[wide[w]]); restSlot.push_back(wide[w]); }
-                    TRY(run_queries(rest, restSlot, nullptr, 0, nullptr, 0));
+                    TRY(run_queries(rest, restSlot, noRows, 0));
                     break;
                 }
-                m = k;
+                m = fc.m;
             }
             std::vector<int32_t> qn(m), ql(m), sl(m);
             std::vector<uint8_t> qt(m);
@@ -1634,41 +1598,33 @@ extern "C" int maple_spr_search_batch(maple_ctx *c, int32_t n, const int32_t *no
                 qb[k] = c->h_tree_dist[node];                          // removedBLen = dist[node] (M:9644)
             }
             if (dbgT) fprintf(stderr, "[maple] t=%.1f ms: wide chunk of %d searches starts\n", tms(tStart, tnow()), m);
-            {
-                size_t need = (size_t)m * nT;
-                if (need > c->s_cache.cap) need = std::min(std::max(need, 2 * c->s_cache.cap), std::max(chunk * (size_t)nT, need));
-                HIPCK(c, c->s_cache.reserve_exact(need));
-            }
+            HIPCK(c, c->s_cache.reserve_exact(plan::cache_reserve((size_t)m * nT, c->s_cache.cap, chunk, nT)));
             if (dbgT) { HIPCK(c, hipStreamSynchronize(c->stream)); fprintf(stderr, "[maple] t=%.1f ms: score table reserved\n", tms(tStart, tnow())); }
             TRY(h2d(c, c->s_u8[3], qt.data(), (size_t)m));
             TRY(h2d(c, c->s_f64[3], qb.data(), (size_t)m));
             if (nF == 1 || rootRows) {
-                int64_t chunkMark = -1;
+                MarkGuard chunkMark{c};
                 if (rootRows) {                                        // candidates (once per tree) and this chunk's removed lists in the root's frame
                     TRY(ensure_cand_root(c));
-                    TRY(maple_arena_mark(c, &chunkMark));
+                    TRY(chunkMark.take());
                     std::vector<int32_t> qf(m);
                     for (int k = 0; k < m; k++) qf[k] = F.frameOf[qn[k]];
                     TRY(lists_to_root_frame(c, ql, qf));
-                    useFin = true;
                 }
                 TRY(h2d(c, c->s_i32[6], ql.data(), (size_t)m));
                 double qBytes = 0.0;                                   // each query list once per launch
                 for (int k = 0; k < m; k++) qBytes += 8.0 * c->h_n_ent[ql[k]] + 8.0 * c->h_n_aux[ql[k]];
                 TRY(fin_reserve((size_t)m));
-                TRY(launch_append_queries(c, c->stream, m, c->s_i32[6].p, c->n_scored, rootRows ? c->s_cand_root.p : c->t_i32[8].p, 0, 0.0, c->s_cache.p, nT,
-                                          rootRows ? c->t_cand_rank.p : c->t_scored_col.p, c->s_u8[3].p, c->s_f64[3].p, MAPLE_K_SPR_SCORE,
-                                          (double)m * c->scored_bytes_total + qBytes, nullptr, nullptr, nullptr, 0, 1, useFin ? c->s_fin_mask.p : nullptr));
-                if (useFin) TRY(fin_prefix(c->stream, 0, (size_t)m));
+                TRY(dense_rows(c->stream, m, c->s_i32[6].p, c->s_u8[3].p, c->s_f64[3].p, qBytes, 0, rootRows, chunkFin));
                 if (dbgT) { HIPCK(c, hipStreamSynchronize(c->stream)); fprintf(stderr, "[maple] t=%.1f ms: scored\n", tms(tStart, tnow())); }
-                if (useFin) finRows = FiniteRows{c->s_fin_mask.p, c->s_fin_prefix.p, finWords};
-                if (useFrontier && useFin && !c->tuning.wideOutsideFrontier && m >= 64) {
+                const ReplayRows chunkRows{c->s_cache.p, nullptr, fin_rows(chunkFin)};
+                if (useFrontier && chunkFin && !c->tuning.wideOutsideFrontier && m >= 64) {
                     // the searches that ran over their budget: back through the frontier tier as whole-tree searches -- their
                     // updating steps batched, their clades scanned over the rows just made (k_fr_replay_wide); what the tier
                     // hands back is replayed one wavefront per search as before, on its own row
                     std::vector<int32_t> rowId(m);
                     for (int k = 0; k < m; k++) rowId[k] = k;
-                    FrontierWide fw2{rowId.data(), c->s_cache.p, finRows, nullptr, 1};
+                    FrontierWide fw2{rowId.data(), c->s_cache.p, chunkRows.fin, nullptr, 1};
                     if (rootRows) {
                         TRY(h2d(c, c->s_frame_parent, F.frameParent.data(), F.frameParent.size()));
                         TRY(h2d(c, c->s_frame_node, F.frameNode.data(), F.frameNode.size()));
@@ -1676,8 +1632,7 @@ extern "C" int maple_spr_search_batch(maple_ctx *c, int32_t n, const int32_t *no
                     }
                     std::vector<SearchOut> part(m);
                     FrontierStats fs2;
-                    const int rcF = frontier_search(c, P, m, qn.data(), 1 << 30, 0, part.data(), poolW, poolA, poolUsed, poolCapW, poolCapA, &fs2, 0, &fw2);
-                    if (rcF != MAPLE_OK) { finRows = FiniteRows{nullptr, nullptr, 0}; return rcF; }
+                    TRY(frontier_search(c, P, m, qn.data(), 1 << 30, 0, part.data(), poolW, poolA, poolUsed, poolCapW, poolCapA, &fs2, 0, &fw2));
                     std::vector<int32_t> qn2, sl2, rows2;
                     for (int k = 0; k < m; k++) {
                         if (part[k].status == FR_STATUS_FALLBACK || part[k].status == -5) { qn2.push_back(qn[k]); sl2.push_back(sl[k]); rows2.push_back(k); }
@@ -1690,27 +1645,19 @@ extern "C" int maple_spr_search_batch(maple_ctx *c, int32_t n, const int32_t *no
                         for (int32_t i : sl) frameWay.push_back(i);
                         qn.clear();
                     }
-                    if (!qn.empty()) rowOverride = &rows2;
-                    const int rcW = qn.empty() ? MAPLE_OK : run_queries(qn, sl, c->s_cache.p, 0, nullptr, 0);
-                    rowOverride = nullptr;
-                    finRows = FiniteRows{nullptr, nullptr, 0};
-                    TRY(rcW);
+                    if (!qn.empty()) TRY(run_queries(qn, sl, ReplayRows{chunkRows.scores, &rows2, chunkRows.fin}, 0));
                 } else if (rootRows) {                                  // (a tail chunk too small for the tier: the frame-by-frame way)
                     for (int32_t i : sl) frameWay.push_back(i);
-                    finRows = FiniteRows{nullptr, nullptr, 0};
-                } else {
-                const int rcW = run_queries(qn, sl, c->s_cache.p, 0, nullptr, 0);
-                finRows = FiniteRows{nullptr, nullptr, 0};
-                TRY(rcW);
-                }
-                if (chunkMark >= 0) TRY(maple_arena_release(c, chunkMark));
+                } else
+                    TRY(run_queries(qn, sl, chunkRows, 0));
+                TRY(chunkMark.release());
                 if (dbgT) fprintf(stderr, "[maple] t=%.1f ms: replayed\n", tms(tStart, tnow()));
             } else {
                 // the removed list in every MAT reference frame, along the paths the traversal itself takes
                 // (passGenomeListThroughBranch up the chain of enclosing frames, M:6844-6847 / 7392, then down into every
                 // other frame from the nearest frame already known, M:7119 / 7342)
-                int64_t mark = 0;
-                TRY(maple_arena_mark(c, &mark));
+                MarkGuard mark{c};
+                TRY(mark.take());
                 std::vector<int32_t> R((size_t)m * nF, -1), cur(m), src, ml, out;
                 std::vector<uint8_t> dir;
                 for (int k = 0; k < m; k++) { cur[k] = F.frameOf[qn[k]]; R[(size_t)k * nF + cur[k]] = ql[k]; }
@@ -1748,18 +1695,15 @@ extern "C" int maple_spr_search_batch(maple_ctx *c, int32_t n, const int32_t *no
                 }
                 if (dbgT) { HIPCK(c, hipStreamSynchronize(c->stream)); fprintf(stderr, "[maple] t=%.1f ms: removed lists in all %d frames\n", tms(tStart, tnow()), nF); }
                 if (c->n_frame_chunks > 0 && m >= 32)
-                    TRY(launch_append_queries(c, c->stream, m, c->s_i32[6].p, c->n_scored, c->t_i32[8].p, 0, 0.0, c->s_cache.p, nT,
-                                              c->t_scored_col.p, c->s_u8[3].p, c->s_f64[3].p, MAPLE_K_SPR_SCORE,
-                                              (double)m * c->scored_bytes_total + qBytes, nullptr, nullptr, c->t_frame_chunks.p,
-                                              c->n_frame_chunks, nF));
+                    TRY(dense_rows(c->stream, m, c->s_i32[6].p, c->s_u8[3].p, c->s_f64[3].p, qBytes, 0, false, false, nF));
                 else
                 TRY(launch_place_score(c, m, nF, c->s_i32[6].p, c->n_scored, c->t_i32[8].p, c->t_scored_frame.p, 0, 0.0,
                                        c->s_cache.p, nT, c->t_scored_col.p, c->s_u8[3].p, c->s_f64[3].p, MAPLE_K_SPR_SCORE,
                                        (double)m * c->scored_bytes_total + qBytes));
                 if (dbgT) { HIPCK(c, hipStreamSynchronize(c->stream)); fprintf(stderr, "[maple] t=%.1f ms: scored\n", tms(tStart, tnow())); }
-                TRY(run_queries(qn, sl, c->s_cache.p, 0, c->s_i32[6].p, nF));
+                TRY(run_queries(qn, sl, ReplayRows{c->s_cache.p, nullptr, fin_rows(false), c->s_i32[6].p, nF}, 0));
                 if (dbgT) fprintf(stderr, "[maple] t=%.1f ms: replayed\n", tms(tStart, tnow()));
-                TRY(maple_arena_release(c, mark));
+                TRY(mark.release());
             }
             w0 += (size_t)m;
         }
@@ -1816,10 +1760,9 @@ extern "C" int maple_spr_search_batch(maple_ctx *c, int32_t n, const int32_t *no
         }
     }
 #endif
-    if (preMark >= 0) TRY(maple_arena_release(c, preMark));             // (the root-frame copies of this call)
-    // (a hinted search that turned out short -- the tree changed around it -- is tried within the budget again next time)
+    TRY(preMark.release());                                             // (the root-frame copies of this call)
     for (size_t i = 0; i < hintedNow.size(); i++)
-        if (hintedNow[i] && ho[i].status == 0 && ho[i].nAppend <= wideBudget / 4) c->h_over_hint[nodes[i]] = 0;
+        if (plan::hint_clear(hintedNow[i] != 0, ho[i].status, ho[i].nAppend, wideBudget)) c->h_over_hint[nodes[i]] = 0;
     if (dbgT) fprintf(stderr, "[maple] t=%.1f ms: results in host memory\n", tms(tStart, tnow()));
     for (int i = 0; i < n; i++) {
         bestNode[i] = ho[i].bestNode; bestScore[i] = ho[i].bestScore;
