@@ -205,8 +205,43 @@ int maple_update_partials(maple_ctx *ctx, int32_t n, int32_t root, const int32_t
                           double *dist, int32_t *lower, int32_t *upRight, int32_t *upLeft, int32_t *totUp, int32_t nChanged,
                           const int32_t *changed, int32_t *nReplaced);
 /* The nodes whose lists (or branch length) the last maple_update_partials replaced, each once, ascending (*n of them; an
- * error if they do not fit in cap): with the nodes of the tree edit itself, what maple_tree_patch has to be told. */
+ * error if they do not fit in cap): with the nodes of the tree edit itself, what maple_tree_patch has to be told.  After
+ * maple_tree_optimize_blens (below): the union over all the repairs of that sweep. */
 int maple_update_partials_touched(maple_ctx *ctx, int32_t cap, int32_t *nodes, int32_t *n);
+
+/* traverseTreeToOptimizeBranchLengths(tree, root, fastPass=...), M:8727-8893 (without `testing`, HnZ or time trees), ONE call of
+ * it, inside the library (maple_amd/csrc/blen_sweep.hip; the logic is maple_amd/csrc/sweep_plan.h).  The columns are the
+ * caller's own, with exactly the meaning and the validation of maple_update_partials; dirty[n] is tree.dirty, in and out.
+ *   Root: without children MAPLE_OK and 0 updates.  Otherwise, if either root child is longer than effectivelyNon0BLen, the grid
+ * search of M:8746-8784 (the first strict maximum wins), then dist[child0] = best and a repair of child0, dist[child1] = the rest
+ * and a repair of child1 -- both whether or not the length moved, as the reference does (the repairs set `dirty`).  The order
+ * swap of the reference's `except:` (M:8798-8810) is not made: a fatal state there is MAPLE_ERR_FATAL.
+ *   Sweep: the reference's visiting order (M:8812-8823 / 8884-8885); dirty[node] is read when the node's turn comes; the estimate
+ * is estimateBranchLengthWithDerivative(upper vector of the parent, passed down through mutList[node] where there is one,
+ * lower[node]); M:8835 / 8869-8883 decide: both lengths zero, or within 1 %: dirty[node] = 0; otherwise dist[node] = the estimate,
+ * one update, and a repair: maple_update_partials with changed = {node}, after which dirty[w] = 1 for every node w it visited
+ * (M:5499-5500, 5410-5411).  fastPass = 1: every dirty branch from the lists as they are, no repair, the id columns untouched.
+ *   *nUpdates: the reference's return value (the root's two children are not counted).  order[]: the nodes handed to a repair, in
+ * order, the root's children first when the grid search ran (fastPass: the nodes whose length changed); *nOrder counts all of
+ * them, order holds the first capOrder (order may be NULL when capOrder is 0).
+ *   Afterwards maple_update_partials_touched reports the union over the whole sweep -- every node with a replaced list or a
+ * changed length: with nothing else, what maple_tree_patch has to be told.
+ *   If the arena runs out in a repair: MAPLE_ERR_NOMEM, and the columns reflect every completed repair.
+ * `chunk` only schedules the estimates (how many go into one launch); no result depends on it. */
+typedef struct {
+    uint32_t structSize;          /* as maple_tuning.structSize: 0 is an error, a shorter struct is read for what it has */
+    double   effectivelyNon0BLen; /* M:3607 */
+    int32_t  fastPass;            /* M:8727: 1 = every dirty branch from the frozen lists, no repair, lists untouched */
+    int32_t  chunk;               /* scheduling only, never results: 0 = the library's adaptive choice,
+                                     k > 0 = exactly k estimates per launch (1 = one at a time) */
+} maple_blen_sweep_params;
+int maple_tree_optimize_blens(maple_ctx *ctx, int32_t n, int32_t root, const int32_t *up, const int32_t *child0,
+                              const int32_t *child1, const uint8_t *isTip, const int32_t *mutList, const int32_t *depth,
+                              double *dist, int32_t *lower, int32_t *upRight, int32_t *upLeft, int32_t *totUp,
+                              uint8_t *dirty /* [n], in/out */, const maple_blen_sweep_params *params, int32_t *nUpdates,
+                              int32_t capOrder, int32_t *order /* may be NULL */, int32_t *nOrder);
+/* since the context was created: estimate launches, estimates computed, estimates used, repairs, sweeps */
+int maple_tree_optimize_blens_stats(maple_ctx *ctx, int64_t *out5);
 
 /* reCalculateAllGenomeLists (M:6013-6347) inside the library: from the tips' lower lists (lower[tip] on entry) every internal
  * node's probVect, deepest level first (M:6031-6200), then probVectUpRight / probVectUpLeft / probVectTotUp of every node from the

@@ -3,7 +3,7 @@
 // the launch attributes the scoring kernels share; and the declarations of the host functions that cross translation units
 // (hidden visibility: not part of the C ABI).  The dispatch over the three model switches, DISPATCH3, is in ctx_host.h.
 // Included by every unit with batch entry points: maple_hip.hip, append_queries.hip, placement.hip, update.hip, spr_batch.hip,
-// debug_abi.hip.
+// debug_abi.hip, blen_sweep.hip.
 #pragma once
 #include "ctx_host.h"
 
@@ -146,6 +146,13 @@ __attribute__((visibility("hidden")))
 int launch_place_score(maple_ctx *c, int nQ, int nF, const int32_t *qFrameLists, int nC, const int32_t *cand, const int32_t *candFrame,
                        int isTip, double bLen, double *out, long long ldOut, const int32_t *outCol, const uint8_t *qTip, const double *qBLen,
                        int kind = MAPLE_K_PLACE_SCORE, double algBytes = 0.0);
+// ---- defined in update.hip -------------------------------------------------------------------------------------------------
+// the nodes the last maple_update_partials visited, with repeats (the reference's updatePartials sets `dirty` for them)
+__attribute__((visibility("hidden")))
+const std::vector<int32_t> &update_partials_visited(maple_ctx *c);
+// the list behind maple_update_partials_touched (a caller that repairs in several calls stores the union here)
+__attribute__((visibility("hidden")))
+std::vector<int32_t> &update_partials_replaced(maple_ctx *c);
 // ---- defined in spr_batch.hip ----------------------------------------------------------------------------------------------
 // the device tree once more from the host copy of its columns (after maple_tree_patch left tables stale)
 __attribute__((visibility("hidden")))

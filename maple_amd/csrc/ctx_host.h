@@ -336,6 +336,7 @@ struct maple_ctx {
     std::unique_ptr<ScratchBase> frontier;   // FrontierScratch of the frontier tier of the SPR search (frontier.hip)
     std::unique_ptr<ScratchBase> witness;    // WitnessScratch of the whole-tree searches' candidate filter (witness.hip)
     std::unique_ptr<ScratchBase> em;         // EmScratch of the EM step (em.hip)
+    std::unique_ptr<ScratchBase> sweep;      // SweepScratch of the branch-length sweep (blen_sweep.hip)
     bool em_frames_valid = false;      // ... its per-frame mutation lists belong to the uploaded tree (dropped by maple_tree_upload)
     bool last_search_frontier_only = false;   // maple_spr_search_visited can report on the last maple_spr_search_batch
     bool nodes_current = false;        // the node records of the SPR search on the device follow every maple_tree_patch

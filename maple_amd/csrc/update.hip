@@ -111,6 +111,9 @@ struct UpdateScratch : ScratchBase {              // per-context, persistent: fl
     std::vector<uint8_t> dLow, dUp, dDist, dCh0, dCh1, inFrontier, inTodo;
     std::vector<int32_t> touched;
     std::vector<int32_t> replacedNodes;   // nodes one of whose four lists (or whose branch length) the last call replaced
+    std::vector<int32_t> visitedNodes;    // nodes the last call visited (with repeats): the changed nodes, every node that entered
+                                          // phase A's frontier or phase B's todo list, the nodes whose length was re-estimated --
+                                          // the ones the reference's updatePartials sets `dirty` for (M:5499-5500, 5410-5411)
     void fit(size_t n)
     {
         if (dLow.size() < n) {
@@ -119,7 +122,7 @@ struct UpdateScratch : ScratchBase {              // per-context, persistent: fl
             touched.clear();
         }
     }
-    void touch(int v) { touched.push_back(v); }
+    void touch(int v) { touched.push_back(v); visitedNodes.push_back(v); }   // (every touched node ends up in phase B's todo list)
     void clear()
     {
         for (int v : touched) dLow[v] = dUp[v] = dDist[v] = dCh0[v] = dCh1[v] = inFrontier[v] = inTodo[v] = 0;
@@ -216,6 +219,7 @@ extern "C" int maple_update_partials(maple_ctx *c, int32_t n, int32_t root, cons
     S.fit((size_t)n);
     S.clear();
     S.replacedNodes.clear();
+    S.visitedNodes.clear();
     int replaced = 0;
     // (the caller's columns are trusted only as far as they are read: every relative that enters the work lists is range-checked)
     bool badNode = false;
@@ -435,6 +439,8 @@ extern "C" int maple_update_partials(maple_ctx *c, int32_t n, int32_t root, cons
                     TRY(maple_blen_batch(c, 1, vu1.data(), &lower[w], &tipc, &t, &isFalse));
                     dist[w] = isFalse ? 0.0 : t;
                     S.replacedNodes.push_back(w);
+                    S.visitedNodes.push_back(w);
+                    if (up[w] >= 0) S.visitedNodes.push_back(up[w]);
                     if (dist[w] != 0.0) { next.push_back(w); done = true; }
                 }
                 if (!done) return fail(c, MAPLE_ERR_FATAL, "None upper vector at node %d and no branch length to lengthen", v);
@@ -474,6 +480,11 @@ extern "C" int maple_update_partials(maple_ctx *c, int32_t n, int32_t root, cons
     *nReplaced = replaced;
     return MAPLE_OK;
 }
+
+// (batch_host.h) for the branch-length sweep, which calls maple_update_partials once per changed branch: what the last call
+// visited, and the list maple_update_partials_touched reports, which the sweep replaces by the union over its repairs
+const std::vector<int32_t> &update_partials_visited(maple_ctx *c) { return update_scratch(c).visitedNodes; }
+std::vector<int32_t> &update_partials_replaced(maple_ctx *c) { return update_scratch(c).replacedNodes; }
 
 // the nodes whose lists (or branch length) the last maple_update_partials replaced, each once, ascending: what a caller
 // has to tell maple_tree_patch about besides its own tree edit

@@ -26,7 +26,7 @@ EXPORTS = [
     "maple_minor_candset", "maple_placement_search_batch", "maple_placement_prepare", "maple_placement_ahead", "maple_placement_ahead_stats", "maple_set_fatal_policy",
     "maple_timing_read_kind", "maple_placement_supports_batch",
     "maple_candset_destroy", "maple_spr_search_visited", "maple_arena_compact", "maple_append_queries_argmax_dev", "maple_comm_unique_id", "maple_comm_init", "maple_argmax_allreduce_dev", "maple_tree_rebuild_lists",
-    "maple_em_expectation", "maple_em_rates",
+    "maple_em_expectation", "maple_em_rates", "maple_tree_optimize_blens", "maple_tree_optimize_blens_stats",
 ]
 
 
@@ -59,6 +59,10 @@ class MaplePlacementParams(C.Structure):
     _fields_ = [("oneMutBLen", C.c_double), ("effectivelyNon0BLen", C.c_double), ("thresholdLogLK", C.c_double),
                 ("thresholdLogLKoptimization", C.c_double), ("thresholdLogLKconsecutivePlacement", C.c_double),
                 ("allowedFails", C.c_int32), ("strictStopRules", C.c_int32), ("onlyFindIdentical", C.c_int32)]
+
+
+class MapleBlenSweepParams(C.Structure):
+    _fields_ = [("structSize", C.c_uint32), ("effectivelyNon0BLen", C.c_double), ("fastPass", C.c_int32), ("chunk", C.c_int32)]
 
 
 class MapleEmTotals(C.Structure):
@@ -421,6 +425,34 @@ class Device:
                                                 _ptr(depth), _ptr(dist), _ptr(lower), _ptr(up_right), _ptr(up_left), _ptr(tot_up),
                                                 len(ch), _ptr(ch), C.byref(n_rep)))
         return int(n_rep.value)
+
+    def optimize_blens(self, root, up, c0, c1, tip, mut, depth, dist, lower, up_right, up_left, tot_up, dirty, effectivelyNon0BLen,
+                       fast_pass=False, chunk=0, cap_order=None):
+        """maple_tree_optimize_blens: one call of traverseTreeToOptimizeBranchLengths on the caller's columns.  ``dist``, the four
+        list-id columns and ``dirty`` (uint8) are updated IN PLACE (C-contiguous arrays, nothing is copied).  Returns
+        (updates, order, nOrder): the reference's return value, the nodes handed to a repair in order (the first ``cap_order``
+        of them, default all) and their full count."""
+        n = len(up)
+        for name, arr, dt in (("up", up, np.int32), ("child0", c0, np.int32), ("child1", c1, np.int32), ("isTip", tip, np.uint8),
+                              ("mutList", mut, np.int32), ("depth", depth, np.int32), ("dist", dist, np.float64),
+                              ("lower", lower, np.int32), ("upRight", up_right, np.int32), ("upLeft", up_left, np.int32),
+                              ("totUp", tot_up, np.int32), ("dirty", dirty, np.uint8)):
+            if not (isinstance(arr, np.ndarray) and arr.dtype == dt and arr.flags.c_contiguous and len(arr) == n):
+                raise ValueError(f"optimize_blens: column {name} must be a C-contiguous {np.dtype(dt).name} array of {n}")
+        cap = n if cap_order is None else int(cap_order)
+        order = np.zeros(max(cap, 1), dtype=np.int32)
+        p = MapleBlenSweepParams(C.sizeof(MapleBlenSweepParams), float(effectivelyNon0BLen), int(bool(fast_pass)), int(chunk))
+        n_upd, n_ord = C.c_int32(0), C.c_int32(0)
+        self._ck(self.lib.maple_tree_optimize_blens(self.h, n, int(root), _ptr(up), _ptr(c0), _ptr(c1), _ptr(tip), _ptr(mut), _ptr(depth),
+                                                    _ptr(dist), _ptr(lower), _ptr(up_right), _ptr(up_left), _ptr(tot_up), _ptr(dirty),
+                                                    C.byref(p), C.byref(n_upd), cap, _ptr(order) if cap else None, C.byref(n_ord)))
+        return int(n_upd.value), order[:min(cap, n_ord.value)].copy(), int(n_ord.value)
+
+    def optimize_blens_stats(self):
+        """maple_tree_optimize_blens_stats, since the context was created: dict(launches, computed, used, repairs, sweeps)."""
+        out = np.zeros(5, dtype=np.int64)
+        self._ck(self.lib.maple_tree_optimize_blens_stats(self.h, _ptr(out)))
+        return dict(zip(("launches", "computed", "used", "repairs", "sweeps"), (int(x) for x in out)))
 
     def debug_wave_append_batch(self, pl, cl, isTipC, bLen):
         """appendProbNode with one wavefront per pair (maple_debug_wave_append_batch); returns (values, kernel ms)."""

@@ -698,6 +698,30 @@ def optimize_branch_lengths(dev: Device, tree: HostTree, effectivelyNon0BLen, di
     return updates, dirty, updated_nodes
 
 
+def optimize_branch_lengths_native(dev: Device, tree: HostTree, effectivelyNon0BLen, dirty=None, fast_pass=False, chunk=0):
+    """traverseTreeToOptimizeBranchLengths(tree, root, fastPass=fast_pass) (M:8727-8893) inside the library
+    (maple_tree_optimize_blens, maple_amd/csrc/blen_sweep.hip): the whole sweep -- root grid search, estimates, the 1 % rule,
+    the repair after every changed branch and the reference's ``dirty`` protocol (a flag is read when the node's turn comes and
+    set for every node a repair visits) -- in one call on the tree's columns, which are built once.  ``tree.dist`` and the four
+    id arrays are updated in place.  ``chunk`` only schedules the estimates (0: the library's adaptive choice).
+    Returns (updates, dirty, order): the reference's return value, the dirty flags afterwards (a list of bool) and the nodes
+    handed to a repair in order, the root's children first when the grid search ran (fast_pass: the nodes whose length
+    changed).  optimize_branch_lengths / optimize_branch_lengths_fast_pass above are the Python forms, kept as the cross-check."""
+    up, c0, c1, tip, depth = tree.columns()
+    flags = np.ones(tree.n, dtype=np.uint8) if dirty is None else np.ascontiguousarray([bool(x) for x in dirty], dtype=np.uint8)
+    dist = tree.dist
+    ids = [np.ascontiguousarray(a, dtype=np.int32) for a in (tree.id_lower, tree.id_upRight, tree.id_upLeft, tree.id_totUp)]
+    mut = np.ascontiguousarray(tree.id_mut, dtype=np.int32)
+    try:
+        updates, order, n_order = dev.optimize_blens(tree.root, up, c0, c1, tip, mut, depth, dist, ids[0], ids[1], ids[2], ids[3], flags,
+                                                     effectivelyNon0BLen, fast_pass=fast_pass, chunk=chunk)
+    finally:
+        # (in place: also after an error the columns hold every completed repair)
+        tree.id_lower, tree.id_upRight, tree.id_upLeft, tree.id_totUp = ids
+    assert n_order == len(order)
+    return updates, [bool(x) for x in flags], [int(v) for v in order]
+
+
 def find_best_root(dev: Device, tree: HostTree, *, strictTopologyStopRules, allowedFailsTopology, thresholdLogLKtopology,
                    thresholdLogLKoptimizationTopology, thresholdLogLKconsecutivePlacement):
     """The search of findBestRoot (M:7730-7840): the relative log-likelihood of re-rooting the tree on each branch.
