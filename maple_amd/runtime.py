@@ -11,76 +11,18 @@ import os
 
 import numpy as np
 
+from .abi import (DEBUG_SIGNATURES, SIGNATURES, MapleBlenSweepParams, MapleEmTotals, MapleError, MapleParams,  # noqa: F401
+                  MaplePlacementParams, MapleSearchParams, MapleTuning, bind)
 from .genome_list import PackedLists, pack_lists, pack_mutations, unpack_list
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libmaple_hip.so")
 
-EXPORTS = [
-    "maple_abi_version", "maple_create", "maple_destroy", "maple_set_tuning", "maple_last_error", "maple_set_model", "maple_get_model",
-    "maple_lists_upload", "maple_lists_update", "maple_lists_sizes", "maple_lists_download", "maple_arena_mark", "maple_arena_release",
-    "maple_arena_stats", "maple_mutations_upload", "maple_append_batch", "maple_merge_batch", "maple_blen_batch",
-    "maple_differ_batch", "maple_pass_branch_batch", "maple_shorten_batch", "maple_root_vector_batch",
-    "maple_evaluate_placement_batch", "maple_update_partials", "maple_update_partials_touched", "maple_tree_patch", "maple_append_batch_dev", "maple_append_queries_dev", "maple_timing_reset", "maple_timing_read", "maple_timing_read_each",
-    "maple_append_algorithmic_bytes", "maple_tree_upload", "maple_spr_search_batch", "maple_minor_batch", "maple_root_prob_batch", "maple_candset_create", "maple_append_candset",
-    "maple_minor_candset", "maple_placement_search_batch", "maple_placement_prepare", "maple_placement_ahead", "maple_placement_ahead_stats", "maple_set_fatal_policy",
-    "maple_timing_read_kind", "maple_placement_supports_batch",
-    "maple_candset_destroy", "maple_spr_search_visited", "maple_arena_compact", "maple_append_queries_argmax_dev", "maple_comm_unique_id", "maple_comm_init", "maple_argmax_allreduce_dev", "maple_tree_rebuild_lists",
-    "maple_em_expectation", "maple_em_rates", "maple_tree_optimize_blens", "maple_tree_optimize_blens_stats",
-]
-
-
-# include/maple_hip_debug.h: measurement aids and test hooks, exported by libmaple_hip_debug.so only (Device(..., debug=True))
-DEBUG_EXPORTS = ["maple_debug_wave_append_batch", "maple_debug_trace_query", "maple_debug_trace_read", "maple_debug_calib_walk",
-                 "maple_debug_calib_write", "maple_debug_gpv_batch", "maple_debug_simplify_batch", "maple_debug_frontier_levels",
-                 "maple_debug_frontier_pass_batch", "maple_debug_live_resources", "maple_debug_score_rows"]
+# the C side as the binding declares it: maple_amd/abi.py (the structs and MapleError are re-exported: callers import them from here)
+EXPORTS, DEBUG_EXPORTS = list(SIGNATURES), list(DEBUG_SIGNATURES)
 LIB_PATH_DEBUG = os.path.join(HERE, "libmaple_hip_debug.so")
 
-
-class MapleParams(C.Structure):
-    _fields_ = [("thresholdProb", C.c_double), ("minBLenSensitivity", C.c_double),
-                ("thresholdDiffForUpdate", C.c_double), ("thresholdFoldChangeUpdate", C.c_double),
-                ("defaultBLen", C.c_double)]
-
-
-class MapleSearchParams(C.Structure):
-    _fields_ = [("strictTopologyStopRules", C.c_int32), ("allowedFailsTopology", C.c_int32),
-                ("thresholdLogLKtopology", C.c_double), ("thresholdTopologyPlacement", C.c_double),
-                ("thresholdLogLKoptimizationTopology", C.c_double), ("thresholdLogLKconsecutivePlacement", C.c_double),
-                ("effectivelyNon0BLen", C.c_double), ("wideSearchBudget", C.c_int32), ("searchTier", C.c_int32)]
-
-
-class MapleTuning(C.Structure):
-    _fields_ = [("structSize", C.c_uint32), ("wavePerItemMax", C.c_int32), ("placementChunkMax", C.c_int32), ("noCladeScan", C.c_int32), ("verbose", C.c_int32),
-                ("wideOutsideFrontier", C.c_int32), ("denseWideScoring", C.c_int32), ("waveAllBelow", C.c_int32), ("noOverHint", C.c_int32), ("noAheadExpansion", C.c_int32), ("noAheadSpeculation", C.c_int32)]
-
-
-class MaplePlacementParams(C.Structure):
-    _fields_ = [("oneMutBLen", C.c_double), ("effectivelyNon0BLen", C.c_double), ("thresholdLogLK", C.c_double),
-                ("thresholdLogLKoptimization", C.c_double), ("thresholdLogLKconsecutivePlacement", C.c_double),
-                ("allowedFails", C.c_int32), ("strictStopRules", C.c_int32), ("onlyFindIdentical", C.c_int32)]
-
-
-class MapleBlenSweepParams(C.Structure):
-    _fields_ = [("structSize", C.c_uint32), ("effectivelyNon0BLen", C.c_double), ("fastPass", C.c_int32), ("chunk", C.c_int32)]
-
-
-class MapleEmTotals(C.Structure):
-    _fields_ = [("counts", C.c_double * 16), ("waitingTimes", C.c_double * 4), ("errorCount", C.c_double), ("totTreeLength", C.c_double),
-                ("observedTotNucsSites", C.c_int64), ("numTips", C.c_int64)]
-
-
 EM_MODELS = {"UNREST": 0, "GTR": 1}
-
-
-class MapleError(RuntimeError):
-    """An error status of libmaple_hip.so; ``code`` is the MAPLE_ERR_* value (include/maple_hip.h)."""
-    ERR_ARG, ERR_HIP, ERR_NOMEM, ERR_STATE, ERR_FATAL = -1, -2, -3, -4, -5
-
-    def __init__(self, msg, code=None):
-        super().__init__(msg)
-        self.code = code
-
 
 _lib = None
 _lib_debug = None
@@ -105,12 +47,7 @@ def load_library(debug=False):
             import torch  # noqa: F401
         except ImportError:
             pass
-        lib = C.CDLL(lib_path)
-        lib.maple_last_error.restype = C.c_char_p
-        for name in EXPORTS + (DEBUG_EXPORTS if debug else []):
-            if not hasattr(lib, name):       # fail early if a declared symbol is not exported
-                raise MapleError(f"{lib_path} does not export {name} (include/maple_hip{'_debug' if name in DEBUG_EXPORTS else ''}.h): "
-                                 "rebuild it with __graft_entry__.build()")
+        lib = bind(C.CDLL(lib_path), debug)      # fails early if a declared symbol is not exported or the ABI version is another
         if debug:
             _lib_debug = lib
         else:
@@ -153,7 +90,7 @@ class Device:
         # (lib: another library with the same C ABI, handed in explicitly -- the tests diff libmaple_hip.so against its CPU twin
         # this way; nothing in the package ever passes one)
         # (debug: libmaple_hip_debug.so -- the same library plus the measurement aids and test hooks of include/maple_hip_debug.h)
-        self.lib = lib if lib is not None else load_library(debug)
+        self.lib = bind(lib, debug, require_all=False) if lib is not None else load_library(debug)
         self.ref_idx = _u8(ref_idx)
         self.lRef = int(len(self.ref_idx))
         if minBLenSensitivity is None:
@@ -161,8 +98,7 @@ class Device:
         p = MapleParams(thresholdProb, minBLenSensitivity, thresholdDiffForUpdate, thresholdFoldChangeUpdate, defaultBLen)
         rf = _f64(root_freqs)
         h = C.c_void_p()
-        rc = self.lib.maple_create(C.byref(h), int(device), self.lRef, _ptr(self.ref_idx), _ptr(rf), C.byref(p),
-                                   C.c_uint64(arena_bytes))
+        rc = self.lib.maple_create(C.byref(h), int(device), self.lRef, _ptr(self.ref_idx), _ptr(rf), C.byref(p), arena_bytes)
         if rc != 0:
             raise MapleError(f"maple_create failed ({rc}): no usable MI355X / HIP runtime; the placement path has no "
                              "CPU fallback")
@@ -200,8 +136,7 @@ class Device:
         Qf = _f64(np.asarray(Q, dtype=np.float64).reshape(16))
         sr = None if siteRates is None else _f64(siteRates)
         er = None if (errorRates is None or not usingErrorRate) else _f64(errorRates)
-        self._ck(self.lib.maple_set_model(self.h, _ptr(Qf), _ptr(sr), int(bool(usingErrorRate)),
-                                          C.c_double(errorRateGlobal or 0.0), _ptr(er)))
+        self._ck(self.lib.maple_set_model(self.h, _ptr(Qf), _ptr(sr), bool(usingErrorRate), errorRateGlobal or 0.0, _ptr(er)))
         self.u = bool(usingErrorRate)
         self.rv, self.ss = sr is not None, er is not None
 
@@ -271,7 +206,7 @@ class Device:
 
     def set_fatal_policy(self, tolerate: bool):
         """tolerate=True: an item that hits a state the reference raises on gets list id -2 instead of failing its batch."""
-        self._ck(self.lib.maple_set_fatal_policy(self.h, int(bool(tolerate))))
+        self._ck(self.lib.maple_set_fatal_policy(self.h, bool(tolerate)))
 
     def mark(self):
         m = C.c_int64()
@@ -279,7 +214,7 @@ class Device:
         return m.value
 
     def release(self, mark):
-        self._ck(self.lib.maple_arena_release(self.h, C.c_int64(mark)))
+        self._ck(self.lib.maple_arena_release(self.h, mark))
 
     def stats(self):
         a, b, c_, d = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
@@ -291,7 +226,7 @@ class Device:
         uploaded tree are gone afterwards (maple_arena_compact)."""
         live = _i32(live)
         new = np.zeros(len(live), np.int32)
-        self._ck(self.lib.maple_arena_compact(self.h, C.c_int64(len(live)), _ptr(live), _ptr(new)))
+        self._ck(self.lib.maple_arena_compact(self.h, len(live), _ptr(live), _ptr(new)))
         return new
 
     def upload_mutations(self, mut_lists):
@@ -342,22 +277,22 @@ class Device:
     def candset_create(self, lists, frame_idx, n_frames):
         lists, frame_idx = _i32(lists), _i32(frame_idx)
         sid = C.c_int32()
-        self._ck(self.lib.maple_candset_create(self.h, len(lists), _ptr(lists), _ptr(frame_idx), int(n_frames), C.byref(sid)))
+        self._ck(self.lib.maple_candset_create(self.h, len(lists), _ptr(lists), _ptr(frame_idx), n_frames, C.byref(sid)))
         return sid.value, len(lists)
 
     def candset_destroy(self, cset):
-        self._ck(self.lib.maple_candset_destroy(self.h, int(cset[0])))
+        self._ck(self.lib.maple_candset_destroy(self.h, cset[0]))
 
     def append_candset(self, cset, frame_lists, isTipC, bLen):
         fl = _i32(frame_lists)
         out = np.zeros(cset[1])
-        self._ck(self.lib.maple_append_candset(self.h, cset[0], _ptr(fl), int(bool(isTipC)), C.c_double(bLen), _ptr(out)))
+        self._ck(self.lib.maple_append_candset(self.h, cset[0], _ptr(fl), bool(isTipC), bLen, _ptr(out)))
         return out
 
     def minor_candset(self, cset, frame_lists, onlyFindIdentical=False):
         fl = _i32(frame_lists)
         out = np.zeros(cset[1], dtype=np.uint8)
-        self._ck(self.lib.maple_minor_candset(self.h, cset[0], _ptr(fl), int(bool(onlyFindIdentical)), _ptr(out)))
+        self._ck(self.lib.maple_minor_candset(self.h, cset[0], _ptr(fl), bool(onlyFindIdentical), _ptr(out)))
         return out
 
     def root_prob_batch(self, lists):
@@ -369,7 +304,7 @@ class Device:
     def minor_batch(self, l1, l2, onlyFindIdentical=False):
         l1, l2 = _i32(l1), _i32(l2)
         out = np.zeros(len(l1), dtype=np.uint8)
-        self._ck(self.lib.maple_minor_batch(self.h, len(l1), _ptr(l1), _ptr(l2), int(bool(onlyFindIdentical)), _ptr(out)))
+        self._ck(self.lib.maple_minor_batch(self.h, len(l1), _ptr(l1), _ptr(l2), bool(onlyFindIdentical), _ptr(out)))
         return out
 
     def pass_branch_batch(self, lists, mutLists, dirIsUp):
@@ -408,7 +343,7 @@ class Device:
         nodes = _i32(nodes)
         cols = [_i32(x) for x in (up, c0, c1)] + [_f64(dist), _u8(tip)] + [_i32(x) for x in (lower, up_right, up_left, tot_up)]
         assert all(len(x) == len(nodes) for x in cols)
-        self._ck(self.lib.maple_tree_patch(self.h, int(n_total), len(nodes), _ptr(nodes), *[_ptr(x) for x in cols]))
+        self._ck(self.lib.maple_tree_patch(self.h, n_total, len(nodes), _ptr(nodes), *[_ptr(x) for x in cols]))
 
     def update_partials(self, root, up, c0, c1, tip, mut, depth, dist, lower, up_right, up_left, tot_up, changed):
         """maple_update_partials: the four list-id columns and ``dist`` are updated IN PLACE (they must be C-contiguous
@@ -421,7 +356,7 @@ class Device:
                 raise ValueError(f"update_partials: column {name} must be a C-contiguous {np.dtype(dt).name} array of {len(up)}")
         ch = _i32(changed)
         n_rep = C.c_int32(0)
-        self._ck(self.lib.maple_update_partials(self.h, len(up), int(root), _ptr(up), _ptr(c0), _ptr(c1), _ptr(tip), _ptr(mut),
+        self._ck(self.lib.maple_update_partials(self.h, len(up), root, _ptr(up), _ptr(c0), _ptr(c1), _ptr(tip), _ptr(mut),
                                                 _ptr(depth), _ptr(dist), _ptr(lower), _ptr(up_right), _ptr(up_left), _ptr(tot_up),
                                                 len(ch), _ptr(ch), C.byref(n_rep)))
         return int(n_rep.value)
@@ -443,7 +378,7 @@ class Device:
         order = np.zeros(max(cap, 1), dtype=np.int32)
         p = MapleBlenSweepParams(C.sizeof(MapleBlenSweepParams), float(effectivelyNon0BLen), int(bool(fast_pass)), int(chunk))
         n_upd, n_ord = C.c_int32(0), C.c_int32(0)
-        self._ck(self.lib.maple_tree_optimize_blens(self.h, n, int(root), _ptr(up), _ptr(c0), _ptr(c1), _ptr(tip), _ptr(mut), _ptr(depth),
+        self._ck(self.lib.maple_tree_optimize_blens(self.h, n, root, _ptr(up), _ptr(c0), _ptr(c1), _ptr(tip), _ptr(mut), _ptr(depth),
                                                     _ptr(dist), _ptr(lower), _ptr(up_right), _ptr(up_left), _ptr(tot_up), _ptr(dirty),
                                                     C.byref(p), C.byref(n_upd), cap, _ptr(order) if cap else None, C.byref(n_ord)))
         return int(n_upd.value), order[:min(cap, n_ord.value)].copy(), int(n_ord.value)
@@ -488,7 +423,7 @@ class Device:
         arrs = [_i32(x) for x in (up, child0, child1)]
         d, tip = _f64(dist), _u8(isTip)
         ls = [_i32(x) for x in (lower, upRight, upLeft, totUp, mutList)]
-        self._ck(self.lib.maple_tree_upload(self.h, n, int(root), _ptr(arrs[0]), _ptr(arrs[1]), _ptr(arrs[2]), _ptr(d),
+        self._ck(self.lib.maple_tree_upload(self.h, n, root, _ptr(arrs[0]), _ptr(arrs[1]), _ptr(arrs[2]), _ptr(d),
                                             _ptr(tip), _ptr(ls[0]), _ptr(ls[1]), _ptr(ls[2]), _ptr(ls[3]), _ptr(ls[4])))
         self.n_nodes = n
 
@@ -505,7 +440,7 @@ class Device:
                    placement=np.zeros(n, np.int32), improvement=np.zeros(n), currentLK=np.zeros(n),
                    nAppend=np.zeros(n, np.int32), status=np.zeros(n, np.int32))
         rpr = np.zeros(n, np.int32) if want_removed_partials else None
-        self._ck(self.lib.maple_spr_search_batch(self.h, n, _ptr(nodes), C.byref(sp), int(ws_entries_per_lane),
+        self._ck(self.lib.maple_spr_search_batch(self.h, n, _ptr(nodes), C.byref(sp), ws_entries_per_lane,
                                                  _ptr(out["bestNode"]), _ptr(out["bestScore"]), _ptr(out["blen"]),
                                                  _ptr(out["placement"]), _ptr(out["improvement"]),
                                                  _ptr(out["currentLK"]), _ptr(out["nAppend"]), _ptr(out["status"]),
@@ -521,7 +456,7 @@ class Device:
             q = np.zeros(cap, np.int32)
             v = np.zeros(cap, np.int32)
             n = C.c_int64()
-            rc = self.lib.maple_spr_search_visited(self.h, C.c_int64(cap), _ptr(q), _ptr(v), C.byref(n))
+            rc = self.lib.maple_spr_search_visited(self.h, cap, _ptr(q), _ptr(v), C.byref(n))
             if rc == MapleError.ERR_ARG and n.value > cap:
                 cap = int(n.value)
                 continue
@@ -586,10 +521,9 @@ class Device:
         off = np.zeros(n + 1, np.int64)
         node, supp, bl = np.zeros(cap, np.int32), np.zeros(cap), np.zeros((cap, 3))
         best, status = np.zeros(n, np.int32), np.zeros(n, np.int32)
-        self._ck(self.lib.maple_placement_supports_batch(self.h, n, _ptr(q), C.byref(pp),
-                                                         C.c_double(thresholdLogLKoptimizationTopology),
-                                                         C.c_double(minBranchSupport), C.c_int64(cap), _ptr(off), _ptr(node),
-                                                         _ptr(supp), _ptr(bl), _ptr(best), _ptr(status)))
+        self._ck(self.lib.maple_placement_supports_batch(self.h, n, _ptr(q), C.byref(pp), thresholdLogLKoptimizationTopology,
+                                                         minBranchSupport, cap, _ptr(off), _ptr(node), _ptr(supp), _ptr(bl),
+                                                         _ptr(best), _ptr(status)))
         out = []
         for g in range(n):
             a, b = off[g], off[g + 1]
@@ -622,7 +556,7 @@ class Device:
         up = _u8(np.broadcast_to(dirIsUp, n))
         out = np.zeros(n, dtype=np.int32)
         grade, same = np.zeros(n, dtype=np.uint8), np.zeros(n, dtype=np.uint8)
-        self._ck(self.lib.maple_debug_frontier_pass_batch(self.h, n, _ptr(lists), _ptr(mutLists), _ptr(up), int(bool(wave_form)),
+        self._ck(self.lib.maple_debug_frontier_pass_batch(self.h, n, _ptr(lists), _ptr(mutLists), _ptr(up), bool(wave_form),
                                                           _ptr(out), _ptr(grade), _ptr(same)))
         return out, grade, same.astype(bool)
 
@@ -641,22 +575,22 @@ class Device:
         mask = np.zeros((nQ, nW), dtype=np.uint64)
         prefix = np.zeros((nQ, nW + 1), dtype=np.int32)
         pairs = C.c_int64(-1)
-        self._ck(self.lib.maple_debug_score_rows(self.h, int(form), nQ, _ptr(q_lists), _ptr(tip), _ptr(bl), nC, _ptr(cands), _ptr(col),
-                                                 C.c_int64(ld), C.c_double(fill), _ptr(out), _ptr(mask), _ptr(prefix), C.byref(pairs)))
+        self._ck(self.lib.maple_debug_score_rows(self.h, form, nQ, _ptr(q_lists), _ptr(tip), _ptr(bl), nC, _ptr(cands), _ptr(col),
+                                                 ld, fill, _ptr(out), _ptr(mask), _ptr(prefix), C.byref(pairs)))
         return out, mask, prefix, pairs.value
 
     def debug_calib_walk(self, nbytes, repeats=1):
         ms = C.c_float()
-        self._ck(self.lib.maple_debug_calib_walk(self.h, C.c_uint64(nbytes), int(repeats), C.byref(ms)))
+        self._ck(self.lib.maple_debug_calib_walk(self.h, nbytes, repeats, C.byref(ms)))
         return ms.value
 
     def debug_calib_write(self, nbytes, mode, repeats=1):
         ms = C.c_float()
-        self._ck(self.lib.maple_debug_calib_write(self.h, C.c_uint64(nbytes), int(mode), int(repeats), C.byref(ms)))
+        self._ck(self.lib.maple_debug_calib_write(self.h, nbytes, mode, repeats, C.byref(ms)))
         return ms.value
 
     def debug_trace_query(self, q):
-        self._ck(self.lib.maple_debug_trace_query(self.h, int(q)))
+        self._ck(self.lib.maple_debug_trace_query(self.h, q))
 
     def debug_trace_read(self):
         n = C.c_int32()
@@ -668,19 +602,14 @@ class Device:
 
     # -- device-resident forms (pointers into HBM, e.g. torch tensors' data_ptr()) ------------------
     def append_batch_dev(self, n, parent_ptr, child_ptr, tip_ptr, blen_ptr, out_ptr, stream=0):
-        self._ck(self.lib.maple_append_batch_dev(self.h, int(n), C.c_void_p(parent_ptr), C.c_void_p(child_ptr),
-                                                 C.c_void_p(tip_ptr), C.c_void_p(blen_ptr), C.c_void_p(out_ptr),
-                                                 C.c_void_p(stream)))
+        self._ck(self.lib.maple_append_batch_dev(self.h, n, parent_ptr, child_ptr, tip_ptr, blen_ptr, out_ptr, stream))
 
     def append_queries_dev(self, nQ, qlist_ptr, nC, cand_ptr, isTipC, bLen, out_ptr, stream=0):
-        self._ck(self.lib.maple_append_queries_dev(self.h, int(nQ), C.c_void_p(qlist_ptr), int(nC), C.c_void_p(cand_ptr),
-                                                   int(bool(isTipC)), C.c_double(bLen), C.c_void_p(out_ptr),
-                                                   C.c_void_p(stream)))
+        self._ck(self.lib.maple_append_queries_dev(self.h, nQ, qlist_ptr, nC, cand_ptr, bool(isTipC), bLen, out_ptr, stream))
 
     def append_queries_argmax_dev(self, nQ, qlist_ptr, nC, cand_ptr, rank_ptr, isTipC, bLen, best_score_ptr, best_idx_ptr, stream=0):
-        self._ck(self.lib.maple_append_queries_argmax_dev(self.h, int(nQ), C.c_void_p(qlist_ptr), int(nC), C.c_void_p(cand_ptr),
-                                                          C.c_void_p(rank_ptr), int(bool(isTipC)), C.c_double(bLen),
-                                                          C.c_void_p(best_score_ptr), C.c_void_p(best_idx_ptr), C.c_void_p(stream)))
+        self._ck(self.lib.maple_append_queries_argmax_dev(self.h, nQ, qlist_ptr, nC, cand_ptr, rank_ptr, bool(isTipC), bLen,
+                                                          best_score_ptr, best_idx_ptr, stream))
 
     def comm_unique_id(self):
         buf = np.zeros(128, dtype=np.uint8)
@@ -688,10 +617,10 @@ class Device:
         return buf
 
     def comm_init(self, world, rank, unique_id):
-        self._ck(self.lib.maple_comm_init(self.h, int(world), int(rank), _ptr(_u8(unique_id))))
+        self._ck(self.lib.maple_comm_init(self.h, world, rank, _ptr(_u8(unique_id))))
 
     def argmax_allreduce_dev(self, n, score_ptr, idx_ptr, stream=0):
-        self._ck(self.lib.maple_argmax_allreduce_dev(self.h, int(n), C.c_void_p(score_ptr), C.c_void_p(idx_ptr), C.c_void_p(stream)))
+        self._ck(self.lib.maple_argmax_allreduce_dev(self.h, n, score_ptr, idx_ptr, stream))
 
     def timing_reset(self):
         self._ck(self.lib.maple_timing_reset(self.h))
@@ -699,7 +628,7 @@ class Device:
     def timing_read_each(self, cap=256):
         ms = np.zeros(cap, dtype=np.float32)
         n = C.c_int32()
-        self._ck(self.lib.maple_timing_read_each(self.h, int(cap), _ptr(ms), C.byref(n)))
+        self._ck(self.lib.maple_timing_read_each(self.h, cap, _ptr(ms), C.byref(n)))
         return ms[: n.value].tolist()
 
     def frontier_levels(self, cap=4096):
@@ -708,7 +637,7 @@ class Device:
         ws, wb = np.zeros(cap, np.int64), np.zeros(cap, np.int64)
         mu, mc = np.zeros(cap, np.float32), np.zeros(cap, np.float32)
         n = C.c_int32()
-        self._ck(self.lib.maple_debug_frontier_levels(self.h, int(cap), _ptr(iu), _ptr(ic), _ptr(mu), _ptr(mc), C.byref(n), _ptr(ws), _ptr(wb)))
+        self._ck(self.lib.maple_debug_frontier_levels(self.h, cap, _ptr(iu), _ptr(ic), _ptr(mu), _ptr(mc), C.byref(n), _ptr(ws), _ptr(wb)))
         k = min(cap, n.value)
         self.last_wave_items = (ws[:k], wb[:k])      # (of the updating items: walked a wavefront each, small / 512-entry class)
         return iu[:k], ic[:k], mu[:k], mc[:k]
@@ -726,8 +655,8 @@ class Device:
         ur, ul, tu = (np.full(n, -1, np.int32) for _ in range(3))
         bad = np.zeros(max(64, n), np.int32)                  # (every node can be named: nothing is dropped)
         nbad = C.c_int32()
-        self._ck(self.lib.maple_tree_rebuild_lists(self.h, n, int(root), _ptr(up), _ptr(c0), _ptr(c1), _ptr(tip), _ptr(mutp), _ptr(dist),
-                                                   _ptr(lower), _ptr(ur), _ptr(ul), _ptr(tu), C.c_double(bump_len), len(bad), _ptr(bad),
+        self._ck(self.lib.maple_tree_rebuild_lists(self.h, n, root, _ptr(up), _ptr(c0), _ptr(c1), _ptr(tip), _ptr(mutp), _ptr(dist),
+                                                   _ptr(lower), _ptr(ur), _ptr(ul), _ptr(tu), bump_len, len(bad), _ptr(bad),
                                                    C.byref(nbad)))
         return lower, ur, ul, tu, np.unique(bad[: min(nbad.value, len(bad))])
 
@@ -756,7 +685,7 @@ class Device:
         sr = np.zeros(L) if getattr(self, "rv", False) else None
         se = np.zeros(L) if getattr(self, "ss", False) else None
         er = C.c_double()
-        self._ck(self.lib.maple_em_rates(self.h, _ptr(nm), int(code), _ptr(Q), _ptr(sr), C.byref(er), _ptr(se)))
+        self._ck(self.lib.maple_em_rates(self.h, _ptr(nm), code, _ptr(Q), _ptr(sr), C.byref(er), _ptr(se)))
         return Q.reshape(4, 4), sr, (er.value if self.u else None), se
 
     def timing_read(self):
@@ -771,7 +700,7 @@ class Device:
     def timing_read_kind(self, kind):
         """(launches, summed HIP-event ms, units of work, algorithmic bytes) of one kind of timed launch since the reset."""
         n, ms, u, b = C.c_int32(), C.c_double(), C.c_double(), C.c_double()
-        self._ck(self.lib.maple_timing_read_kind(self.h, int(kind), C.byref(n), C.byref(ms), C.byref(u), C.byref(b)))
+        self._ck(self.lib.maple_timing_read_kind(self.h, kind, C.byref(n), C.byref(ms), C.byref(u), C.byref(b)))
         return n.value, ms.value, u.value, b.value
 
     def append_algorithmic_bytes(self, parent, child=None, child_once=False):
@@ -779,5 +708,5 @@ class Device:
         ch = None if child is None else _i32(child)
         b = C.c_uint64()
         self._ck(self.lib.maple_append_algorithmic_bytes(self.h, len(parent), _ptr(parent), _ptr(ch),
-                                                         int(bool(child_once)), C.byref(b)))
+                                                         bool(child_once), C.byref(b)))
         return b.value

@@ -23,14 +23,14 @@ def declared_symbols(header="maple_hip.h"):
 def test_library_exports_every_declared_symbol():
     import __graft_entry__ as g
     g.build()
-    from maple_amd import runtime
+    from maple_amd import abi, runtime
     lib = runtime.load_library()
     names = declared_symbols()
     assert len(names) >= 25
     for n in names:
         assert hasattr(lib, n), f"{n} declared in include/maple_hip.h but not exported"
     assert set(runtime.EXPORTS) <= set(names)
-    assert lib.maple_abi_version() == 4
+    assert lib.maple_abi_version() == abi.ABI_VERSION
     # the product library is the operator boundary and nothing else: the measurement aids and test hooks of
     # include/maple_hip_debug.h are exported by libmaple_hip_debug.so only, which also has everything above
     dbg_names = declared_symbols("maple_hip_debug.h")
