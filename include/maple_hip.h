@@ -413,6 +413,22 @@ int maple_em_expectation(maple_ctx *ctx, const int32_t *nMinor /* [n], NULL = 0 
 int maple_em_rates(maple_ctx *ctx, const int32_t *nMinor, int model, double *Q16, double *siteRates,
                    double *errorRateGlobal, double *siteErrRates);
 
+/* ---- the likelihood of the tree ----
+ * calculateTreeLikelihood(tree, root), M:9721-9779 (without checkCorrectness and HnZ) on the tree of the last
+ * maple_tree_upload / maple_tree_patch and the model of the last maple_set_model (MAPLE_ERR_STATE without either).  One lane per
+ * internal node merges the two children's lower lists for their likelihood contribution and writes no list
+ * (maple_amd/csrc/tree_lk.hip); a child -- or the root -- with a mutation list is passed up through it first, into lists under an
+ * arena mark of the library's own, released before the call returns (MAPLE_ERR_NOMEM if the arena cannot hold them; the arena is
+ * then as it was).  nMinor as for maple_em_expectation; a node's tip flag is the uploaded isTip.  *rootLK =
+ * findProbRoot(probVect[root]); nodeLK[v] = the Lkcontribution of internal node v (M:9756), 0.0 for leaves and for slots the root
+ * does not reach; *totalLK = the contributions added one after the other from 0.0 in the reference's order (post-order: the
+ * children[v][0] subtree, the children[v][1] subtree, v), then *rootLK -- added on the host, the same bits on every call.  A root
+ * without children: totalLK = rootLK.  A merge the reference would find None (M:9762), or an underflow of its running factor:
+ * MAPLE_ERR_FATAL, maple_last_error names the node.  Joins the traversal made ahead by maple_placement_ahead first and leaves
+ * its rows alone. */
+int maple_tree_log_lk(maple_ctx *ctx, const int32_t *nMinor /* [n], NULL = all 0 */, double *totalLK,
+                      double *rootLK /* may be NULL */, double *nodeLK /* [n], may be NULL */);
+
 /* ---- device-resident forms (inputs already in HBM; asynchronous on `stream`) ---
  * `stream` is the caller's hipStream_t, used verbatim: NULL is the legacy default stream (what
  * torch.cuda.current_stream().cuda_stream is unless the caller switched streams), so the launch is ordered with the

@@ -121,6 +121,7 @@ SIGNATURES = {
     "maple_em_expectation": ("int", ("maple_ctx *", "const int32_t *", "maple_em_totals *", "double *", "double *", "double *", "double *",
         "double *")),
     "maple_em_rates": ("int", ("maple_ctx *", "const int32_t *", "int", "double *", "double *", "double *", "double *")),
+    "maple_tree_log_lk": ("int", ("maple_ctx *", "const int32_t *", "double *", "double *", "double *")),
     "maple_append_batch_dev": ("int", ("maple_ctx *", "int32_t", "const int32_t *", "const int32_t *", "const uint8_t *", "const double *",
         "double *", "void *")),
     "maple_append_queries_dev": ("int", ("maple_ctx *", "int32_t", "const int32_t *", "int32_t", "const int32_t *", "int", "double", "double *",

@@ -128,6 +128,18 @@ struct Writer {                        // builds one packed list
     }
 };
 
+// A Writer's interface that stores nothing: the entries and aux doubles the list would have had are counted (k_tree_lk)
+struct CountSink {
+    int n = 0, na = 0;
+    __device__ inline void put(int type, int, int, bool hasD0, double, bool hasD1, double, bool, const double *)
+    {
+        n++;
+        na += (hasD0 ? 1 : 0) + (hasD1 ? 1 : 0) + (type == 6 ? 4 : 0);
+    }
+    __device__ inline void bare(int, int, int) { n++; }
+    __device__ inline void copy(const Ent &e, int type, int, int) { put(type, 0, 0, e.hasD0, 0, e.hasD1, 0, false, nullptr); }
+};
+
 // ---- getPartialVec (M:4073-4141) -----------------------------------------------------
 // O vector moved along a branch: v + t*(Q v) going down, v + t*(Q^T v) going up
 template <class C> __device__ inline void gpv_vec(const C &c, double r, const double *v, double t, bool up, double *out)
@@ -516,9 +528,11 @@ __device__ inline double append_walk_gathered(const Ctx<RV, U, SS> &c, ListRef P
 
 // ---- mergeVectors (M:4446-4859) -----------------------------------------------------------
 // returns number of entries written, -1 for the reference's None, -2 for a fatal state
-template <bool RV, bool U, bool SS>
+// Sink: where the merged list goes -- a Writer, or a CountSink when only the likelihood is wanted (the step only ever writes to
+// it: put / bare, never a read back)
+template <bool RV, bool U, bool SS, class Sink>
 __device__ int merge_walk(const Ctx<RV, U, SS> &c, ListRef L1, double bLen1, bool tip1, ListRef L2, double bLen2,
-                          bool tip2, bool upDown, bool wantLK, int numMinor1, int numMinor2, Writer &o, double *outLK)
+                          bool tip2, bool upDown, bool wantLK, int numMinor1, int numMinor2, Sink &o, double *outLK)
 {
     typedef Ctx<RV, U, SS> CT;
     const int lRef = c.m.lRef;

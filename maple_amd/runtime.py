@@ -344,6 +344,7 @@ class Device:
         cols = [_i32(x) for x in (up, c0, c1)] + [_f64(dist), _u8(tip)] + [_i32(x) for x in (lower, up_right, up_left, tot_up)]
         assert all(len(x) == len(nodes) for x in cols)
         self._ck(self.lib.maple_tree_patch(self.h, n_total, len(nodes), _ptr(nodes), *[_ptr(x) for x in cols]))
+        self.n_nodes = n_total
 
     def update_partials(self, root, up, c0, c1, tip, mut, depth, dist, lower, up_right, up_left, tot_up, changed):
         """maple_update_partials: the four list-id columns and ``dist`` are updated IN PLACE (they must be C-contiguous
@@ -687,6 +688,19 @@ class Device:
         er = C.c_double()
         self._ck(self.lib.maple_em_rates(self.h, _ptr(nm), code, _ptr(Q), _ptr(sr), C.byref(er), _ptr(se)))
         return Q.reshape(4, 4), sr, (er.value if self.u else None), se
+
+    def tree_log_lk(self, n_minor=None, per_node=False):
+        """calculateTreeLikelihood (M:9721-9779) on the uploaded tree inside the library (maple_tree_log_lk): (totalLK, rootLK), with
+        per_node also the contribution of every internal node (float64 [n]; 0.0 for leaves and unreachable slots).
+        n_minor[v] = len(minorSequences[v]), None = all 0."""
+        nm = None if n_minor is None else _i32(n_minor)
+        n = getattr(self, "n_nodes", 0)                      # (0: no tree yet, the library says so)
+        if nm is not None and n and len(nm) != n:
+            raise MapleError(f"n_minor has {len(nm)} entries, the uploaded tree {n} nodes", MapleError.ERR_ARG)
+        total, root = C.c_double(), C.c_double()
+        node = np.zeros(n) if per_node and n else None
+        self._ck(self.lib.maple_tree_log_lk(self.h, _ptr(nm), C.byref(total), C.byref(root), _ptr(node)))
+        return (total.value, root.value, node) if per_node else (total.value, root.value)
 
     def timing_read(self):
         """(number of timed *_dev launches since the last reset, their summed HIP-event time in ms)."""

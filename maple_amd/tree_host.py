@@ -257,6 +257,13 @@ def tree_log_likelihood(dev: Device, tree: HostTree):
         dev.release(mark)
 
 
+def tree_log_likelihood_native(dev: Device, tree: HostTree):
+    """calculateTreeLikelihood (M:9721-9779) in one call of the library (maple_tree_log_lk, maple_amd/csrc/tree_lk.hip):
+    (total, root) like tree_log_likelihood, bit for bit.  It runs on the tree the library holds: keeping that current
+    (upload_topology / sync) is the caller's job, as for estimate_rates; the minor-sequence counts come from ``tree.n_minor``."""
+    return dev.tree_log_lk(tree.n_minor if any(tree.n_minor) else None)
+
+
 def rebuild_genome_lists(dev: Device, tree: HostTree, native=True):
     """reCalculateAllGenomeLists (M:6013-6347) on the device for a tree WITH MAT local references: given only the
     tips' lower lists (already uploaded by HostTree.upload) recompute probVect of every internal node (pass 1) and
