@@ -146,7 +146,7 @@ __attribute__((visibility("hidden")))
 int launch_place_score(maple_ctx *c, int nQ, int nF, const int32_t *qFrameLists, int nC, const int32_t *cand, const int32_t *candFrame,
                        int isTip, double bLen, double *out, long long ldOut, const int32_t *outCol, const uint8_t *qTip, const double *qBLen,
                        int kind = MAPLE_K_PLACE_SCORE, double algBytes = 0.0);
-// ---- defined in update.hip -------------------------------------------------------------------------------------------------
+// ---- defined in update.hip (both are lists of update_plan::Scratch: update_plan.h holds the level loops that fill them) -----
 // the nodes the last maple_update_partials visited, with repeats (the reference's updatePartials sets `dirty` for them)
 __attribute__((visibility("hidden")))
 const std::vector<int32_t> &update_partials_visited(maple_ctx *c);

@@ -534,8 +534,9 @@ def test_update_partials_matches_reference(uname):
             twin_replaced = update_genome_lists(dev, twin, [v], native=False)
         except RuntimeError as e:
             # the Python cross-check stops where the upper pass meets an inconsistent zero-length branch (the reference's
-            # updateBLen inside the from-parent direction, M:5522-5600); the library's loop handles it (update.hip) and is
-            # still compared with the reference's own repair below
+            # updateBLen inside the from-parent direction, M:5522-5600); the library's loop handles it (update_plan.h: that arm is
+            # pinned on the CPU by test_update_plan.py::test_none_in_the_upper_pass) and is still compared with the reference's
+            # own repair below
             if "updateBLen" not in str(e):
                 raise
             twin = None
