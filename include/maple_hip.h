@@ -30,6 +30,7 @@
 #ifndef MAPLE_HIP_H
 #define MAPLE_HIP_H
 #include <stdint.h>
+#include "maple_hip_root_search.h"   /* maple_root_search_params, the parameter struct of maple_tree_find_best_root */
 
 #ifdef __cplusplus
 extern "C" {
@@ -428,6 +429,33 @@ int maple_em_rates(maple_ctx *ctx, const int32_t *nMinor, int model, double *Q16
  * its rows alone. */
 int maple_tree_log_lk(maple_ctx *ctx, const int32_t *nMinor /* [n], NULL = all 0 */, double *totalLK,
                       double *rootLK /* may be NULL */, double *nodeLK /* [n], may be NULL */);
+
+/* ---- the search for the best root ----
+ * The search of findBestRoot(tree, root), M:7730-7848 (without time trees and HnZ), on the tree of the last maple_tree_upload /
+ * maple_tree_patch and the model of the last maple_set_model (MAPLE_ERR_STATE without either): the relative log-likelihood of
+ * re-rooting on every branch, made level by level on the device (maple_amd/csrc/root_search.hip), and the reference's depth-first
+ * traversal with its stop rules replayed over them on the host.  nMinor and the tip flags as for maple_tree_log_lk.
+ * *bestNode, *bestLKdiff, *nodesVisited = the reference's bestNode, bestLKdiff, nodesVisitedRoot when its `while nodesToVisit` loop
+ * ends.  bestNodes / bestScores = its bestNodes dict at that moment in insertion order, the root with 0.0 first: *nBest counts all
+ * of them, the arrays hold the first capBest (capBest = n never cuts it short).  branchScore[v] = the `score` of M:7808 for rooting
+ * on the branch above v, for every branch the level loop scored -- whether or not the replayed traversal reaches it; NaN for the
+ * root, the root's two children, slots the root does not reach, and every branch at or below a rooting the reference abandons in
+ * its `except:` (M:7838: a merge without result; the other side of the same node is still tried, the call returns MAPLE_OK).
+ * The reference's in-place shorten(upVect) at M:7819, which depends on the traversal's order, is not made: shorten is applied only
+ * after a pass down through a mutation list (M:7845).  A root without children, or whose children are both leaves: bestNode =
+ * root, 0.0, 1 visited, bestNodes = {root: 0.0}.  structSize as in maple_tuning: 0 is an error, a shorter struct is read for what it
+ * has; thresholdLogLKtopology is already multiplied by log(lRef).
+ * Joins the traversal made ahead by maple_placement_ahead first and leaves its rows alone; the temporaries live under an arena mark
+ * of the call's own, released on every path (MAPLE_ERR_NOMEM: the arena is as it was).
+ * Not here, left with the caller (tree surgery): the re-rooting itself (reRootTree, M:7850-7884), the
+ * re-keying of bestNodes around it, reCalculateAllGenomeLists after it and the aBayes root supports (M:7887-7900). */
+/* maple_root_search_params: include/maple_hip_root_search.h, included above */
+int maple_tree_find_best_root(maple_ctx *ctx, const int32_t *nMinor /* [n], NULL = all 0 */,
+                              const maple_root_search_params *params,
+                              int32_t *bestNode, double *bestLKdiff, int32_t *nodesVisited,
+                              double *branchScore /* [n], may be NULL */,
+                              int32_t capBest, int32_t *bestNodes, double *bestScores /* may be NULL when capBest is 0 */,
+                              int32_t *nBest);
 
 /* ---- device-resident forms (inputs already in HBM; asynchronous on `stream`) ---
  * `stream` is the caller's hipStream_t, used verbatim: NULL is the legacy default stream (what

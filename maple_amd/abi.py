@@ -1,5 +1,5 @@
 """What the binding knows of the C side (include/maple_hip.h, include/maple_hip_debug.h), stated once: the ABI version, the
-error codes, the six structs, and the signature of every entry point.  maple_amd/runtime.py calls through what bind() declares;
+error codes, the six structs of maple_hip.h and the one of maple_hip_root_search.h, and the signature of every entry point.  maple_amd/runtime.py calls through what bind() declares;
 tests/test_abi_signatures.py compares all of it with the two headers, so a change of either side that the other misses fails there.
 """
 import ctypes as C
@@ -49,8 +49,16 @@ class MapleEmTotals(C.Structure):
                 ("observedTotNucsSites", C.c_int64), ("numTips", C.c_int64)]
 
 
+class MapleRootSearchParams(C.Structure):
+    _fields_ = [("structSize", C.c_uint32), ("strictTopologyStopRules", C.c_int32), ("allowedFailsTopology", C.c_int32),
+                ("thresholdLogLKtopology", C.c_double), ("thresholdLogLKoptimizationTopology", C.c_double),
+                ("thresholdLogLKconsecutivePlacement", C.c_double)]
+
+
 STRUCTS = {"maple_params": MapleParams, "maple_search_params": MapleSearchParams, "maple_tuning": MapleTuning,
            "maple_placement_params": MaplePlacementParams, "maple_blen_sweep_params": MapleBlenSweepParams, "maple_em_totals": MapleEmTotals}
+# include/maple_hip_root_search.h (tests/test_abi_root_search_params.py): passed by reference as a plain pointer
+ROOT_SEARCH_STRUCTS = {"maple_root_search_params": MapleRootSearchParams}
 SCALARS = {"int": C.c_int, "int32_t": C.c_int32, "uint32_t": C.c_uint32, "int64_t": C.c_int64, "uint64_t": C.c_uint64,
            "uint8_t": C.c_uint8, "float": C.c_float, "double": C.c_double}
 
@@ -122,6 +130,8 @@ SIGNATURES = {
         "double *")),
     "maple_em_rates": ("int", ("maple_ctx *", "const int32_t *", "int", "double *", "double *", "double *", "double *")),
     "maple_tree_log_lk": ("int", ("maple_ctx *", "const int32_t *", "double *", "double *", "double *")),
+    "maple_tree_find_best_root": ("int", ("maple_ctx *", "const int32_t *", "const maple_root_search_params *", "int32_t *", "double *",
+        "int32_t *", "double *", "int32_t", "int32_t *", "double *", "int32_t *")),
     "maple_append_batch_dev": ("int", ("maple_ctx *", "int32_t", "const int32_t *", "const int32_t *", "const uint8_t *", "const double *",
         "double *", "void *")),
     "maple_append_queries_dev": ("int", ("maple_ctx *", "int32_t", "const int32_t *", "int32_t", "const int32_t *", "int", "double", "double *",

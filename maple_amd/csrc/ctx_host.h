@@ -338,9 +338,11 @@ struct maple_ctx {
     std::unique_ptr<ScratchBase> em;         // EmScratch of the EM step (em.hip)
     std::unique_ptr<ScratchBase> sweep;      // SweepScratch of the branch-length sweep (blen_sweep.hip)
     std::unique_ptr<ScratchBase> treelk;     // TreeLkScratch of the tree likelihood (tree_lk.hip)
+    std::unique_ptr<ScratchBase> rootsearch; // RootSearchScratch of the root search (root_search.hip)
     bool em_frames_valid = false;      // ... its per-frame mutation lists belong to the uploaded tree (dropped by maple_tree_upload)
     bool tree_lk_valid = false;        // the post-order item list of maple_tree_log_lk belongs to the tree as it stands (dropped by
                                        // maple_tree_upload and maple_tree_patch)
+    bool root_search_valid = false;    // the level lists of maple_tree_find_best_root belong to the tree as it stands (dropped likewise)
     bool last_search_frontier_only = false;   // maple_spr_search_visited can report on the last maple_spr_search_batch
     bool nodes_current = false;        // the node records of the SPR search on the device follow every maple_tree_patch
     bool tree_stale = false;           // maple_tree_patch changed the host copy of the tree; the device tables of the SPR search

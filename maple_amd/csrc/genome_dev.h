@@ -641,45 +641,76 @@ template <class C> __device__ bool differ_walk(const C &c, ListRef L1, ListRef L
 }
 
 // ---- findProbRoot (M:4865-4912): log-likelihood of a lower list (already in the root frame) at the root ----
+// One entry of the walk: `pos` = the positions consumed before it, entPos = its last position.  False when the running factor
+// underflowed (the walk's value is then -inf).  Shared by root_prob_walk, which reads the entries of a stored list, and
+// RootProbSink, which is handed them as a merge produces them.
+template <bool RV, bool U, bool SS>
+__device__ __forceinline__ bool root_prob_entry(const Ctx<RV, U, SS> &c, int type, int entPos, bool hasD0, bool flag, const double *vec,
+                                                int &pos, double &logLK, double &logFactor)
+{
+    const double *rf = c.rf;
+    const int32_t *cb = c.m.cumulativeBases;
+    if (U && type < 5 && hasD0 && flag) {
+        if (type == 4) { logLK += c.m.rootFreqsLogErrorCumulative[entPos] - c.m.rootFreqsLogErrorCumulative[pos]; pos = entPos; }
+        else {
+            double er = c.err(pos);
+            logFactor *= (sel4(rf, type) * (1.0 - 1.33333 * er) + 0.33333 * er);
+            pos += 1;
+        }
+    } else if (type == 4) {
+        for (int i = 0; i < 4; i++) logLK += c.m.rootFreqsLog[i] * (cb[entPos * 4 + i] - cb[pos * 4 + i]);
+        pos = entPos;
+    } else if (type < 4) { logLK += c.m.rootFreqsLog[type]; pos += 1; }
+    else if (type == 6) {
+        double tot = 0.0;
+        for (int i = 0; i < 4; i++) tot += rf[i] * vec[i];
+        logFactor *= tot;
+        pos += 1;
+    } else pos = entPos;
+    if (logFactor <= c.m.minimumCarryOver) {
+        if (logFactor < 2.2250738585072014e-308) return false;
+        logLK += log(logFactor);
+        logFactor = 1.0;
+    }
+    return true;
+}
+
 template <bool RV, bool U, bool SS> __device__ double root_prob_walk(const Ctx<RV, U, SS> &c, ListRef L)
 {
     const int lRef = c.m.lRef;
-    const double *rf = c.rf;
-    const int32_t *cb = c.m.cumulativeBases;
     Cursor a;
     a.init(L);
     double logLK = 0.0, logFactor = 1.0;
     int pos = 0;
     for (;;) {
         const Ent &e = a.e;
-        if (U && e.type < 5 && e.hasD0 && e.flag) {
-            if (e.type == 4) { logLK += c.m.rootFreqsLogErrorCumulative[e.pos] - c.m.rootFreqsLogErrorCumulative[pos]; pos = e.pos; }
-            else {
-                double er = c.err(pos);
-                logFactor *= (sel4(rf, e.type) * (1.0 - 1.33333 * er) + 0.33333 * er);
-                pos += 1;
-            }
-        } else if (e.type == 4) {
-            for (int i = 0; i < 4; i++) logLK += c.m.rootFreqsLog[i] * (cb[e.pos * 4 + i] - cb[pos * 4 + i]);
-            pos = e.pos;
-        } else if (e.type < 4) { logLK += c.m.rootFreqsLog[e.type]; pos += 1; }
-        else if (e.type == 6) {
-            double tot = 0.0;
-            for (int i = 0; i < 4; i++) tot += rf[i] * e.vec[i];
-            logFactor *= tot;
-            pos += 1;
-        } else pos = e.pos;
-        if (logFactor <= c.m.minimumCarryOver) {
-            if (logFactor < 2.2250738585072014e-308) return -INFINITY;
-            logLK += log(logFactor);
-            logFactor = 1.0;
-        }
+        if (!root_prob_entry(c, e.type, e.pos, e.hasD0, e.flag, e.vec, pos, logLK, logFactor)) return -INFINITY;
         if (pos == lRef) break;
         a.next();
     }
     logLK += log(logFactor);
     return logLK;
 }
+
+// A Writer's interface that stores nothing and runs findProbRoot over the entries as they come (k_root_new): the merged list whose
+// root probability is wanted is never stored.  value() after the merge that fed it has reached the end of the genome.
+template <bool RV, bool U, bool SS> struct RootProbSink {
+    const Ctx<RV, U, SS> &c;
+    int n = 0, na = 0;
+    int pos = 0;
+    double logLK = 0.0, logFactor = 1.0;
+    bool dead = false;
+    __device__ explicit RootProbSink(const Ctx<RV, U, SS> &c_) : c(c_) {}
+    __device__ inline void put(int type, int entPos, int, bool hasD0, double, bool hasD1, double, bool flag, const double *vec)
+    {
+        n++;
+        na += (hasD0 ? 1 : 0) + (hasD1 ? 1 : 0) + (type == 6 ? 4 : 0);
+        if (!dead && !root_prob_entry(c, type, entPos, hasD0, flag, vec, pos, logLK, logFactor)) dead = true;
+    }
+    __device__ inline void bare(int type, int entPos, int) { put(type, entPos, 0, false, 0, false, 0, false, nullptr); }
+    __device__ inline void copy(const Ent &e, int type, int entPos, int) { put(type, entPos, 0, e.hasD0, 0, e.hasD1, 0, e.flag, e.vec); }
+    __device__ inline double value() const { return dead ? -INFINITY : logLK + log(logFactor); }
+};
 
 // ---- isMinorSequence (M:5919-6004): 1 = list2 is at most as informative as list1, 2 = the opposite, 0 = neither ----
 __device__ inline int minor_walk(int lRef, ListRef L1, ListRef L2, bool onlyFindIdentical)

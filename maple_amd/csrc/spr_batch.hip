@@ -439,6 +439,7 @@ extern "C" int maple_tree_upload(maple_ctx *c, int32_t n, int32_t root, const in
     c->h_tree_upLeft.assign(upLeft, upLeft + n);
     c->em_frames_valid = false;
     c->tree_lk_valid = false;
+    c->root_search_valid = false;
     if (!c->place) c->place.reset(new PlaceMeta());
     c->place->valid = false;
     c->place->rootVect = -1;
@@ -648,6 +649,7 @@ extern "C" int maple_tree_patch(maple_ctx *c, int32_t nTotal, int32_t nTouched, 
     c->dtree.n = nTotal;
     c->tree_stale = true;
     c->tree_lk_valid = false;
+    c->root_search_valid = false;
     c->scan_valid = false;
     c->cand_root_end = -1;
     c->h_clade.clear();

@@ -12,7 +12,7 @@ import os
 import numpy as np
 
 from .abi import (DEBUG_SIGNATURES, SIGNATURES, MapleBlenSweepParams, MapleEmTotals, MapleError, MapleParams,  # noqa: F401
-                  MaplePlacementParams, MapleSearchParams, MapleTuning, bind)
+                  MaplePlacementParams, MapleRootSearchParams, MapleSearchParams, MapleTuning, bind)
 from .genome_list import PackedLists, pack_lists, pack_mutations, unpack_list
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -701,6 +701,31 @@ class Device:
         node = np.zeros(n) if per_node and n else None
         self._ck(self.lib.maple_tree_log_lk(self.h, _ptr(nm), C.byref(total), C.byref(root), _ptr(node)))
         return (total.value, root.value, node) if per_node else (total.value, root.value)
+
+    def tree_find_best_root(self, n_minor=None, *, strictTopologyStopRules, allowedFailsTopology, thresholdLogLKtopology,
+                            thresholdLogLKoptimizationTopology, thresholdLogLKconsecutivePlacement, cap_best=None, struct_size=None):
+        """The search of findBestRoot (M:7730-7848) on the uploaded tree inside the library (maple_tree_find_best_root):
+        (bestNode, bestLKdiff, nodesVisited, branchScore [n] float64 with NaN where no rooting was scored, bestNodes int32 [k],
+        bestScores float64 [k], nBest) -- the reference's bestNodes dict in insertion order, k = min(nBest, cap_best);
+        cap_best None = room for every node.  n_minor[v] = len(minorSequences[v]), None = all 0.  struct_size: what the params
+        struct claims as its size (None: its real size)."""
+        nm = None if n_minor is None else _i32(n_minor)
+        n = getattr(self, "n_nodes", 0)                      # (0: no tree yet, the library says so)
+        if nm is not None and n and len(nm) != n:
+            raise MapleError(f"n_minor has {len(nm)} entries, the uploaded tree {n} nodes", MapleError.ERR_ARG)
+        p = MapleRootSearchParams(C.sizeof(MapleRootSearchParams) if struct_size is None else struct_size, int(bool(strictTopologyStopRules)),
+                                  int(min(max(allowedFailsTopology, -(1 << 31)), (1 << 31) - 1)), thresholdLogLKtopology,
+                                  thresholdLogLKoptimizationTopology, thresholdLogLKconsecutivePlacement)
+        cap = n if cap_best is None else int(cap_best)
+        best, visited, n_best, diff = C.c_int32(), C.c_int32(), C.c_int32(), C.c_double()
+        score = np.full(n, np.nan) if n else None
+        nodes = np.zeros(cap, np.int32) if cap > 0 else None
+        scores = np.zeros(cap) if cap > 0 else None
+        self._ck(self.lib.maple_tree_find_best_root(self.h, _ptr(nm), C.byref(p), C.byref(best), C.byref(diff), C.byref(visited),
+                                                    _ptr(score), cap, _ptr(nodes), _ptr(scores), C.byref(n_best)))
+        k = min(cap, n_best.value)
+        return (best.value, diff.value, visited.value, score, np.zeros(0, np.int32) if nodes is None else nodes[:k],
+                np.zeros(0) if scores is None else scores[:k], n_best.value)
 
     def timing_read(self):
         """(number of timed *_dev launches since the last reset, their summed HIP-event time in ms)."""

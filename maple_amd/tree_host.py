@@ -860,3 +860,18 @@ def find_best_root(dev: Device, tree: HostTree, *, strictTopologyStopRules, allo
     finally:
         dev.set_fatal_policy(False)
         dev.release(mark)
+
+
+def find_best_root_native(dev: Device, tree: HostTree, *, strictTopologyStopRules, allowedFailsTopology, thresholdLogLKtopology,
+                          thresholdLogLKoptimizationTopology, thresholdLogLKconsecutivePlacement):
+    """The search of findBestRoot (M:7730-7848) in one call of the library (maple_tree_find_best_root,
+    maple_amd/csrc/root_search.hip): find_best_root's 4-tuple, bit for bit, with bestNodes an ordered dict.  It runs on the tree
+    the library holds: keeping that current (upload_topology / sync) is the caller's job, as for tree_log_likelihood_native; the
+    minor-sequence counts come from ``tree.n_minor``."""
+    best, diff, visited, _, nodes, scores, n_best = dev.tree_find_best_root(
+        tree.n_minor if any(tree.n_minor) else None, strictTopologyStopRules=strictTopologyStopRules,
+        allowedFailsTopology=allowedFailsTopology, thresholdLogLKtopology=thresholdLogLKtopology,
+        thresholdLogLKoptimizationTopology=thresholdLogLKoptimizationTopology,
+        thresholdLogLKconsecutivePlacement=thresholdLogLKconsecutivePlacement)
+    assert n_best == len(nodes)
+    return best, diff, dict(zip((int(v) for v in nodes), (float(x) for x in scores))), visited
