@@ -21,6 +21,16 @@ extern "C" {
 int maple_debug_frontier_levels(maple_ctx *ctx, int32_t cap, int64_t *itemsUpdating, int64_t *itemsCached, float *msUpdating,
                                 float *msCached, int32_t *n, int64_t *waveItemsSmall /* or NULL */, int64_t *waveItemsBig /* or NULL */);
 
+/* The items that the wavefront-wide kernels of that pass (k_fr_updating_wave_s / k_fr_updating_wave) handed whole to lane 0.
+ * counts[3]: because [0] a list does not fit the staging areas, [1] the item is scored without the parent's upper list or without
+ * probVectTotUp (the on-the-spot merge of M:7198-7200), [2] it sits at the root and still updates lists (rootVector).  A library
+ * built with -DMAPLE_SPR_PROFILE sets *profiled = 1 and fills slots[3 * 8] -- per kind of item (small / 512 class: 0 1 by the
+ * wavefront, 2 3 lane 0: no fit, 4 5 lane 0: on-the-spot probVectTotUp, 6 7 lane 0: root) its count, total ms and slowest ms --
+ * and, for the first cap levels, the slowest wavefront-wide item of the level (ms) and its kind; otherwise *profiled = 0 and those
+ * are zero. */
+int maple_debug_frontier_wave_paths(maple_ctx *ctx, int64_t *counts, int32_t cap, float *levelSlowestMs, int32_t *levelSlowestSlot,
+                                    double *slots, int32_t *profiled);
+
 /* appendProbNode for n (parent list, child list) pairs with ONE WAVEFRONT per pair (maple_amd/csrc/wave_dev.h: the walk cut
  * along its merge path, the factors of all steps at once, the running product in walk order): the same results as
  * maple_append_batch bit for bit; *ms (optional) = kernel time.  A test and timing aid. */

@@ -220,6 +220,16 @@ extern "C" int maple_debug_frontier_levels(maple_ctx *c, int32_t cap, int64_t *i
     return rc;
 }
 
+extern "C" int maple_debug_frontier_wave_paths(maple_ctx *c, int64_t *counts, int32_t cap, float *levelSlowestMs, int32_t *levelSlowestSlot,
+                                               double *slots, int32_t *profiled)
+{
+    if (!c || !counts || cap < 0 || (cap > 0 && (!levelSlowestMs || !levelSlowestSlot)) || !slots || !profiled) return MAPLE_ERR_ARG;
+    int prof = 0;
+    const int rc = frontier_wave_paths(c, (long long *)counts, cap, levelSlowestMs, (int *)levelSlowestSlot, slots, &prof);
+    *profiled = prof;
+    return rc;
+}
+
 // ---- passGenomeListThroughBranch of a removed list as the frontier tier of the SPR search runs it (frontier_dev.h) ---------------
 // The tier's two forms -- one lane per item (fpass_removed: fpass_store + shorten_would_merge) and one wavefront per item
 // (wave_pass with `removed` set) -- are reached in the product only from inside a search on a tree with MAT local references.

@@ -15,26 +15,34 @@
     WaveLdsC &W = *reinterpret_cast<WaveLdsC *>(L.baux);                   // (appendProbNode's staging: baux is free by then)
     static_assert(sizeof(WaveLdsC) <= sizeof(L.baux), "LDS alias");
     const long long lo = (long long)fp.ctr->loU;
-    // the level's items that go a wavefront each, listed by k_fr_sort_level (Class::perm): dealt to the wavefronts one at a time
+    // the level's items that go a wavefront each, listed by k_fr_sort_level (Class::perm, in any order): dealt to the wavefronts one at
+    // a time
     const long long nHeavy = (long long)(fp.ctr->*Class::count);
     (void)heavyMin;
     // (what the launch did, for the roofline of the bench line -- the same account as k_fr_updating's: the two lists every
     // mergeVectors reads and the one it writes; kept by lane 0, one atomic per wavefront at the end)
     unsigned long long nU = 0, bU = 0;
-    for (long long kk = blockIdx.x; kk < nHeavy; kk += gridDim.x) {
+    for (;;) {
+        // (by ticket, not by stride: a wavefront on a slow item -- long lists next to the root -- holds nothing back but that item.
+        // Lane 0 takes the ticket, one atomic per item; nobody waits for anybody.  k_fr_snap_u resets the counter with the list.)
+        unsigned long long tk = 0;
+        if (lane == 0) tk = atomicAdd(&fp.ctr->ticket[Class::profCls], 1ull);
+        const long long kk = (long long)(((unsigned long long)(uint32_t)__shfl((int)(tk >> 32), 0, 64) << 32) | (uint32_t)__shfl((int)tk, 0, 64));
+        if (kk >= nHeavy) break;
         nU++;
 #ifdef MAPLE_SPR_PROFILE
         const long long tItem0 = wall_clock64();
         int profCls = Class::profCls;
         struct ProfEnd {                                                    // (booked on every way out of the item's block)
-            const FPools &fp; const long long t0; int &cls;
+            const FPools &fp; const long long t0; int &cls; const int level;
             __device__ ~ProfEnd() {
                 if ((threadIdx.x & 63) == 0) {
                     const unsigned long long dt = (unsigned long long)(wall_clock64() - t0);
                     atomicAdd(&fp.ctr->dbgWCnt[cls], 1ull); atomicAdd(&fp.ctr->dbgWT[cls], dt); atomicMax(&fp.ctr->dbgWMax[cls], dt);
+                    atomicMax(&fp.ctr->dbgLvlW[level], (dt << 4) | (unsigned long long)cls);
                 }
             }
-        } profEnd{fp, tItem0, profCls};
+        } profEnd{fp, tItem0, profCls, min(max(fp.ctr->nLevels - 1, 0), FR_PROF_LEVELS - 1)};
 #endif
         {
             const long long i = lo + (fp.*Class::perm)[kk];
@@ -57,7 +65,7 @@
 #ifdef MAPLE_SPR_PROFILE
                 profCls += 2;
 #endif
-                if (lane == 0) fr_upd_item_lane_call(c, av, T, P, fp, budget, laneBase + blockIdx.x, i, &bU);
+                if (lane == 0) { atomicAdd(&fp.ctr->wavePath[FR_WP_LANE0_FIT], 1ull); fr_upd_item_lane_call(c, av, T, P, fp, budget, laneBase + blockIdx.x, i, &bU); }
                 wave_sync();
                 continue;
             }
@@ -164,8 +172,15 @@
                 const FList lo2 = flist(av, fp, hOther);
                 const FList lvu = fvalid(vectUp) ? flist(av, fp, vectUp) : FList{nullptr, nullptr, 0, 0};
                 if (scored) {
-                    if (!fvalid(vectUp) || r1.totUp < 0) {                  // (the on-the-spot probVectTotUp of M:7198-7200: one lane)
-                        if (lane == 0) fr_upd_item_lane_call(c, av, T, P, fp, budget, laneBase + blockIdx.x, i, &bU);
+                    if (!fvalid(vectUp) || r1.totUp < 0) {
+                        // The on-the-spot probVectTotUp of M:7198-7200 (and a parent without an upper list for this side): one lane.
+                        // Left as it is: the headline tree has NO such item (FCtr::wavePath, profiles/late_levels_before.txt: 0 of a
+                        // round's 72 000 wavefront-wide items) -- every branch next to its root is long enough to carry a
+                        // probVectTotUp.  Small trees with a zero-length branch at the root do meet it.
+#ifdef MAPLE_SPR_PROFILE
+                        profCls += 4;
+#endif
+                        if (lane == 0) { atomicAdd(&fp.ctr->wavePath[FR_WP_LANE0_SPOT], 1ull); fr_upd_item_lane_call(c, av, T, P, fp, budget, laneBase + blockIdx.x, i, &bU); }
                         wave_sync();
                         continue;
                     }
@@ -228,8 +243,12 @@
                                                  : push1(false, upT, (int)r1.whichChild + 1, -1, 0.0, midProb, pr.fails, pr.pathBest, hRpr, crossU);
                             }
                         } else if (upd) {                                   // t1 is the root and the item still updates: rootVector, one lane
-                            // (nothing was pushed or stored yet that the one-lane walk would not redo)
-                            if (lane == 0) fr_upd_item_lane_call(c, av, T, P, fp, budget, laneBase + blockIdx.x, i, &bU);
+                            // (nothing was pushed or stored yet that the one-lane walk would not redo.  Left as it is for the same
+                            // reason: the headline tree's rounds hold no such item among the wavefront-wide ones)
+#ifdef MAPLE_SPR_PROFILE
+                            profCls += 6;
+#endif
+                            if (lane == 0) { atomicAdd(&fp.ctr->wavePath[FR_WP_LANE0_ROOT], 1ull); fr_upd_item_lane_call(c, av, T, P, fp, budget, laneBase + blockIdx.x, i, &bU); }
                             wave_sync();
                             continue;
                         } else

@@ -32,5 +32,7 @@ int frontier_search(maple_ctx *c, const SearchParams &P, int m, const int32_t *n
                     const uint8_t *overHint = nullptr);   // host, per search (or null): leave at once as "over the budget" (status -5) -- the caller knows it would
 __attribute__((visibility("hidden"))) int frontier_export(maple_ctx *c, long long cap, int32_t *q, int32_t *node, long long *n);
 __attribute__((visibility("hidden")))
+int frontier_wave_paths(maple_ctx *c, long long *counts, int cap, float *lvlMs, int *lvlSlot, double *slots, int *profiled);
+__attribute__((visibility("hidden")))
 int frontier_level_profile(maple_ctx *c, int cap, long long *itemsU, long long *itemsC, float *msU, float *msC, int *n,
                            long long *waveSmall = nullptr, long long *waveBig = nullptr);

@@ -168,6 +168,7 @@ __global__ void k_fr_snap_u(FCtr *ctr, long long capU, long long capR, long long
         ctr->bigUsed = 0;
         const unsigned long long heavySmall = ctr->permHeavy, heavyBig = ctr->permHeavy2;
         ctr->permDown = ctr->permUp = ctr->permDownB = ctr->permUpB = ctr->permHeavy = ctr->permHeavy2 = 0;
+        ctr->ticket[0] = ctr->ticket[1] = 0;                                // (the wavefront-wide kernels' dealing starts over with the lists)
         if (lvl) {
             const int l = ctr->nLevels++;
             if (l < maxLevels) { lvl[FR_LVL * l] = ctr->loU; lvl[FR_LVL * l + 1] = ctr->hiU; lvl[FR_LVL * l + 6] = lvl[FR_LVL * l + 7] = 0; }
@@ -1112,6 +1113,10 @@ struct FrontierScratch : ScratchBase {
     std::vector<unsigned long long> lastLvl;        // [levels][4]: the level ranges of the last call (frontier_level_profile)
     std::vector<size_t> lastSlotsU, lastSlotsC;    // ... and the timing slots of its level kernels
     long long lastU = -1, lastC = -1, lastR = 0;     // items of the last call (for frontier_export), -1: none
+    // ... and what its wavefront-wide kernels did (frontier_wave_paths): FCtr::wavePath; with MAPLE_SPR_PROFILE the dbgW slots
+    // (count, ticks, slowest) and the slowest wavefront-wide item of every level
+    unsigned long long lastWavePath[FR_WP_N] = {};
+    std::vector<unsigned long long> lastProfW, lastProfLvl;
     plan::FrontierNeeds need;                        // what the last call that counts asked of the pools (plan::remember_frontier)
     FPools lastPools{};
     int capE = 0;                                    // entries of a per-lane scratch slab
@@ -1331,6 +1336,13 @@ int frontier_search(maple_ctx *c, const SearchParams &P, int m, const int32_t *n
         HIPCK(c, hipEventRecord(a0, s));
         k_fr_sort_level<<<512, FR_BLOCK, 0, s>>>(av, T, fp, pl.heavyMin, pl.bigMin);
         TRY(stage("k_fr_sort_level"));
+        // (A level is these four dependent launches and k_fr_snap_u, and each of them starts only when wavefront slots and registers
+        // come free under k_fr_cached -- 128 VGPRs x 4 wavefronts is a SIMD's whole file: a late level of 2 items takes 0.2-1.1 ms, one
+        // of 5 400 items 0.5-7.4 ms, while all the wavefront-wide items of levels 6-23 together are 1.8 ms of work for 1 536
+        // wavefronts and the slowest item of a level 0.04-0.28 ms (profiles/late_levels_before.txt).  The one-lane paths left in the
+        // wavefront kernels -- a list beyond the staging, the on-the-spot probVectTotUp, rootVector at the root: FCtr::wavePath --
+        // take 0 items of a headline round and stay as they are.  The wavefront kernels take their items by ticket, so the
+        // wavefronts that did get a slot drain the level's list: k_fr_updating's share of a step 74.9 -> 70.6 ms.)
         // (the level's three kinds of list-updating items behind each other on this stream.  The 512-entry class on a stream of its
         // own was measured: 175 ms per round instead of 152 -- a third side stream shares a hardware queue with the cached-regime
         // kernel's and runs behind it.)
@@ -1388,7 +1400,7 @@ int frontier_search(maple_ctx *c, const SearchParams &P, int m, const int32_t *n
     for (;;) {
         for (int g = 0; g < pl.groupLevels; g++) {
             TRY(u_level());
-            for (int k2 = 0; k2 < 2; k2++) TRY(c_launch());
+            for (int k2 = plan::cached_behind(pl, levels - 1); k2 > 0; k2--) TRY(c_launch());
         }
         HIPCK(c, hipGetLastError());
         HIPCK(c, hipMemcpyAsync(&hc, fp.ctr, sizeof(FCtr), hipMemcpyDeviceToHost, s));
@@ -1509,8 +1521,10 @@ int frontier_search(maple_ctx *c, const SearchParams &P, int m, const int32_t *n
                 hc.dbgC[0], (double)hc.dbgC[5] / hc.dbgC[0], hc.dbgC[1] * 1e-2 / hc.dbgC[0], hc.dbgC[2] * 1e-2 / hc.dbgC[0],
                 (double)hc.dbgC[6] / std::max(1.0, (double)hc.dbgC[5]), (double)hc.dbgC[4] / hc.dbgC[0], hc.dbgC[3] * 1e-2 / hc.dbgC[0]);
     {
-        const char *nm[4] = {"small class", "512 class", "small class, one lane (a list does not fit)", "512 class, one lane (a list does not fit)"};
-        for (int b = 0; b < 4; b++)
+        const char *nm[8] = {"small class", "512 class", "small class, one lane (a list does not fit / no upper list)", "512 class, one lane (a list does not fit / no upper list)",
+                             "small class, one lane (on-the-spot probVectTotUp)", "512 class, one lane (on-the-spot probVectTotUp)",
+                             "small class, one lane (at the root)", "512 class, one lane (at the root)"};
+        for (int b = 0; b < 8; b++)
             if (hc.dbgWCnt[b]) fprintf(stderr, "[maple] wavefront-wide updating items, %s: %llu items, mean %.3f ms, slowest %.3f ms\n", nm[b],
                                        hc.dbgWCnt[b], hc.dbgWT[b] * 1e-5 / hc.dbgWCnt[b], hc.dbgWMax[b] * 1e-5);
     }
@@ -1528,6 +1542,13 @@ int frontier_search(maple_ctx *c, const SearchParams &P, int m, const int32_t *n
     F.need = plan::remember_frontier(F.need, m, anyWide && wide->forceWide, hc.usedU, hc.usedC, hc.usedR, hc.nLists, hc.usedW, hc.usedA, hc.overflow != 0);
     F.lastU = std::min((long long)hc.usedU, fp.capU); F.lastC = std::min((long long)hc.usedC, fp.capCC);
     F.lastR = std::min((long long)hc.usedR, fp.capC - fp.capCC); F.lastPools = fp;
+    std::copy(hc.wavePath, hc.wavePath + FR_WP_N, F.lastWavePath);
+#ifdef MAPLE_SPR_PROFILE
+    F.lastProfW.assign(hc.dbgWCnt, hc.dbgWCnt + 8);
+    F.lastProfW.insert(F.lastProfW.end(), hc.dbgWT, hc.dbgWT + 8);
+    F.lastProfW.insert(F.lastProfW.end(), hc.dbgWMax, hc.dbgWMax + 8);
+    F.lastProfLvl.assign(hc.dbgLvlW, hc.dbgLvlW + FR_PROF_LEVELS);
+#endif
     {
         const int nl = std::min(std::max(levels, launchesC), fp.maxLevels);
         F.lastLvl.assign((size_t)nl * FR_LVL, 0ull);
@@ -1567,6 +1588,27 @@ int frontier_export(maple_ctx *c, long long cap, int32_t *q, int32_t *node, long
     HIPCK(c, hipMemcpyAsync(q, F->expQ.p, (size_t)tot * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     HIPCK(c, hipMemcpyAsync(node, F->expNode.p, (size_t)tot * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     HIPCK(c, hipStreamSynchronize(c->stream));
+    return MAPLE_OK;
+}
+
+// The items the wavefront-wide kernels of the last frontier_search handed to lane 0, by reason: counts[3] = FCtr::wavePath.
+// In a build with MAPLE_SPR_PROFILE (*profiled = 1) also slots[3 * 8] = per dbgW slot the items, their total ms and the slowest
+// one's ms, and for the first min(cap, levels) levels the slowest wavefront-wide item (ms) and its slot; zeros otherwise.
+int frontier_wave_paths(maple_ctx *c, long long *counts, int cap, float *lvlMs, int *lvlSlot, double *slots, int *profiled)
+{
+    FrontierScratch *F = static_cast<FrontierScratch *>(c->frontier.get());
+    if (!F) return fail(c, MAPLE_ERR_STATE, "no frontier search to report on");
+    for (int k = 0; k < FR_WP_N; k++) counts[k] = (long long)F->lastWavePath[k];
+    *profiled = F->lastProfW.empty() ? 0 : 1;
+    for (int b = 0; b < 8; b++) {
+        slots[b] = *profiled ? (double)F->lastProfW[b] : 0.0;
+        slots[8 + b] = *profiled ? F->lastProfW[8 + b] * 1e-5 : 0.0;        // (wall_clock64: 100 MHz)
+        slots[16 + b] = *profiled ? F->lastProfW[16 + b] * 1e-5 : 0.0;
+    }
+    for (int l = 0; l < cap; l++) {
+        const unsigned long long v = l < (int)F->lastProfLvl.size() ? F->lastProfLvl[l] : 0ull;
+        lvlMs[l] = (float)((v >> 4) * 1e-5); lvlSlot[l] = (int)(v & 15ull);
+    }
     return MAPLE_OK;
 }
 

@@ -94,6 +94,11 @@ struct FRec { int32_t q, ref; double optimized, top, bottom, app; int32_t ok;
 #define FR_FRAMES_EVENT (-4)            // ... and the branch beat the running best when it was visited (M:7087 applies to that list)
 #define FR_FRAMES (-2)                  // (a record of k_fr_replay_wide whose removed list is still in its seed's frame: k_fr_wide_frames)
 
+// FCtr::wavePath: items the wavefront-wide kernels handed whole to lane 0, by reason -- a list does not fit the staging; scored
+// without the parent's upper list or without probVectTotUp; at the root, still updating
+enum { FR_WP_LANE0_FIT = 0, FR_WP_LANE0_SPOT = 1, FR_WP_LANE0_ROOT = 2, FR_WP_N = 3 };
+#define FR_PROF_LEVELS 64              // levels of FCtr::dbgLvlW (later ones are booked on the last)
+
 struct FCtr {                          // device-side bookkeeping of the level loop
     // (what every lane READS at the start of a kernel, and each counter the lanes bump, on cache lines of their own)
     alignas(128) unsigned long long loU;
@@ -134,11 +139,20 @@ struct FCtr {                          // device-side bookkeeping of the level l
     unsigned long long bytesC;         // cached-regime items scored by k_fr_cached and their SURVEY 8d bytes (8 E + 8 A + 8)
     int32_t overflow, nLevels, nLevelsC;
     int32_t fbReason[8];               // searches handed to the one-lane kernel by the exact walk, by reason (k_fr_replay; printed with verbose)
+    // The wavefront-wide kernels (fr_wave_items_body.inc).  ticket: the next item of the level's list of each size class, taken
+    // by whichever wavefront is free (reset by k_fr_snap_u with the lists).  wavePath: the items those kernels handed to lane 0,
+    // counted per call (FR_WP_*; maple_debug_frontier_wave_paths reads them).
+    alignas(128) unsigned long long ticket[2];
+    alignas(128) unsigned long long wavePath[FR_WP_N];
 #ifdef MAPLE_SPR_PROFILE
+    unsigned long long dbgLvlW[FR_PROF_LEVELS];          // per level, the slowest wavefront-wide item: ticks << 4 | its dbgW slot
     unsigned long long dbgCnt[8], dbgT[8], dbgMax[8];   // k_fr_updating's one-lane items by size (entries of the two lists): count, ticks, slowest
     unsigned long long dbgC[8];        // k_fr_cached per wavefront-iteration: iterations, ticks before the walk (item, search, node, list table),
                                        // ticks of the walk, ticks after it (rule, pushes), the longest lane's entries (two lists), scored lanes
-    unsigned long long dbgWCnt[4], dbgWT[4], dbgWMax[4]; // the wavefront-wide items: small class, 512 class, walked by lane 0 alone (small / 512)
+    // the wavefront-wide items, small class / 512 class: 0 1 plain, 2 3 walked by lane 0 alone (a list does not fit, or the parent
+    // has no upper list), 4 5 with the
+    // on-the-spot probVectTotUp, 6 7 at the root (rootVector)
+    unsigned long long dbgWCnt[8], dbgWT[8], dbgWMax[8];
 #endif
 };
 
@@ -573,7 +587,8 @@ __device__ inline bool fr_wave_fits(const ArenaViewS &av, const DevTree &T, cons
 }
 // The two size classes of the wavefront-wide items: what k_fr_sort_level sorts by and the kernels of fr_wave_items_body.inc are
 // compiled for.  wuIn / capW: the staging of WaveUpdLds / WaveLds (wave_update.h, wave_dev.h); perm / count: the level's list of
-// the class's items and their number; profCls: the class's slot of FCtr::dbgW* (MAPLE_SPR_PROFILE).
+// the class's items and their number; profCls: the class's index -- its ticket counter (FCtr::ticket) and its slot of FCtr::dbgW*
+// (MAPLE_SPR_PROFILE).
 struct WaveSmall {                     // 128-entry lists: 27 KB of LDS per wavefront, five wavefronts per compute unit (k_fr_updating_wave_s)
     static constexpr int wuIn = 128, capW = 256, profCls = 0;
     static constexpr int32_t *FPools::*perm = &FPools::perm3;

@@ -10,6 +10,10 @@
 #include <cstdint>
 #include <vector>
 
+#ifndef MAPLE_FR_CACHED_EARLY
+#define MAPLE_FR_CACHED_EARLY 4        // cached launches behind each of a whole round's first updating levels (FrontierPlan::cachedBehindEarly)
+#endif
+
 namespace maple {
 namespace plan {
 
@@ -56,7 +60,17 @@ struct FrontierPlan {
     double room;
     // launch geometry
     int gridN, gridCached, heavyMin, bigMin, gridWave, gridWaveSmall, groupLevels, gridLayout, waveAllBelow;
+    // cached-regime launches queued behind the publication of an updating level: cachedBehindEarly behind each of the first
+    // cachedEarlyLevels levels, cachedBehind behind every later one (cached_behind below)
+    int cachedBehind, cachedBehindEarly, cachedEarlyLevels;
 };
+
+// Every cached launch takes a snapshot of what is complete when it starts, so any count >= 1 gives the same searches; a launch more
+// is two more layout launches at the end of the round.
+static inline int cached_behind(const FrontierPlan &p, int level)
+{
+    return level < p.cachedEarlyLevels ? p.cachedBehindEarly : p.cachedBehind;
+}
 
 static inline size_t grow(size_t want, size_t cap) { return want <= cap ? cap : std::max(want, cap + cap / 2); }
 
@@ -168,6 +182,12 @@ static inline FrontierPlan plan_frontier(const FrontierPlanIn &in)
     // the host looks at the counters every few levels: a handful of searches (the re-search of a proposed move) is over after a few
     // levels and each look costs them less than the levels it saves; a whole round runs ~20 updating levels
     p.groupLevels = m <= 64 ? 2 : 8;
+    // two cached launches behind every level: the cached subtrees are deeper than the updating chain is long.  The first six levels
+    // of a whole round hold 95 % of its updating items, last 6-9 ms each, and a cached launch next to them is over in 0.5-2 ms:
+    // the stream then idles until the next level publishes its roots.  MAPLE_FR_CACHED_EARLY launches behind each of those
+    // (measured on the headline, medians of 8 runs each in two sessions: 2 -> 121.2 ms per step, 3 -> 118.5, 4 -> 118.2, the same
+    // order in both sessions; profiles/late_levels_bench.md); a handful of searches keeps two throughout.
+    p.cachedBehind = 2; p.cachedBehindEarly = m <= 64 ? 2 : MAPLE_FR_CACHED_EARLY; p.cachedEarlyLevels = 6;
     p.gridLayout = (int)std::min<long long>(1024, std::max<long long>(64, (long long)m / 64));   // (~100 small launches: the grid goes with the batch)
     p.waveAllBelow = in.waveAllBelow > 0 ? in.waveAllBelow : (in.waveAllBelow < 0 ? 0 : 49152);
     return p;

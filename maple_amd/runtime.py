@@ -643,6 +643,24 @@ class Device:
         self.last_wave_items = (ws[:k], wb[:k])      # (of the updating items: walked a wavefront each, small / 512-entry class)
         return iu[:k], ic[:k], mu[:k], mc[:k]
 
+    WAVE_PATHS = ("lane0_no_fit", "lane0_spot_tot_up", "lane0_root")
+    WAVE_SLOTS = ("small class", "512 class", "small class, lane 0 (a list does not fit)", "512 class, lane 0 (a list does not fit)",
+                  "small class, lane 0 (on-the-spot probVectTotUp)", "512 class, lane 0 (on-the-spot probVectTotUp)",
+                  "small class, lane 0 (root item)", "512 class, lane 0 (root item)")
+
+    def frontier_wave_paths(self, cap=64):
+        """Of the last frontier-tier pass (maple_debug_frontier_wave_paths): a dict of the items the wavefront-wide kernels handed to
+        lane 0, by WAVE_PATHS, and -- from a library built with MAPLE_SPR_PROFILE, else None -- per WAVE_SLOTS (count, total ms, slowest ms) and
+        per level (slowest wavefront-wide item's ms, its slot)."""
+        counts, slots = np.zeros(3, np.int64), np.zeros(24, np.float64)
+        ms, slot = np.zeros(cap, np.float32), np.zeros(cap, np.int32)
+        prof = C.c_int32()
+        self._ck(self.lib.maple_debug_frontier_wave_paths(self.h, _ptr(counts), cap, _ptr(ms), _ptr(slot), _ptr(slots), C.byref(prof)))
+        paths = dict(zip(self.WAVE_PATHS, counts.tolist()))
+        if not prof.value:
+            return paths, None, None
+        return paths, slots.reshape(3, 8).T.copy(), (ms, slot)
+
     def tree_rebuild_lists(self, root, up, c0, c1, tip, mut, dist, lower, bump_len=0.0):
         """reCalculateAllGenomeLists (M:6013-6347) with the level loop inside the library (maple_tree_rebuild_lists): returns
         (lower, upRight, upLeft, totUp, bad) -- new id columns, ``dist`` (float64, contiguous) updated in place when bump_len > 0,
