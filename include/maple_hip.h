@@ -430,6 +430,31 @@ int maple_em_rates(maple_ctx *ctx, const int32_t *nMinor, int model, double *Q16
 int maple_tree_log_lk(maple_ctx *ctx, const int32_t *nMinor /* [n], NULL = all 0 */, double *totalLK,
                       double *rootLK /* may be NULL */, double *nodeLK /* [n], may be NULL */);
 
+/* ---- probable sequencing errors per sample ----
+ * calculateErrorProbabilities(tree, root, file, minErrorProb, namesInTree), M:9783-10020 (--estimateErrors; without time trees and
+ * HnZ), as arrays: on the tree of the last maple_tree_upload / maple_tree_patch and the model of the last maple_set_model
+ * (MAPLE_ERR_STATE without either, or when the model has no error rate: the reference calls it only under an error model).
+ * Leaves are the nodes without children (nodeIsLeaf, as in maple_em_expectation) in the order the reference's traversal meets
+ * them -- depth first, children[v][0] before children[v][1]: leafNode[k] is the node id, *nLeaves their number (capLeaves smaller
+ * than that: MAPLE_ERR_ARG with *nLeaves set; leafNode holds capLeaves, outOff capLeaves + 1 entries).  The records of leaf k are
+ * [outOff[k], outOff[k+1]), positions ascending: outPos = the 1-based position the reference writes, outAllele = the index into
+ * allelesList or 4 for its "X", outProb = the posterior probability that the leaf's difference from its parent at that site is a
+ * sequencing error, for every site where the reference's `>= minErrorProb` test holds.  A leaf with nMinor > 0 has no records
+ * (M:9805-9807: the reference lists its minor sequences' names instead), and neither has a root without children, on which the
+ * reference fails (up[root] is None).  nMinor as for maple_em_expectation (a negative one: MAPLE_ERR_ARG).
+ * Sizing: cap = the capacity of the three record arrays; cap == 0 counts only (the arrays may be NULL): outOff, *nLeaves and
+ * *nRecords are filled and the call returns MAPLE_OK; 0 < cap < *nRecords: MAPLE_ERR_ARG with offsets and counts valid.
+ * One lane walks each leaf's (parent upper list, lower list) pair, twice: a launch that counts, a scan of the counts on the host, a
+ * launch that writes (maple_amd/csrc/error_probs.hip) -- no float atomics, the same bytes on every call.  The parent list of a
+ * leaf with a mutation list is passed down through it first, into lists under an arena mark of the call's own, released on every
+ * path (MAPLE_ERR_NOMEM if the arena cannot hold them; the arena is then as it was).  A zero denominator, where the reference
+ * raises ZeroDivisionError (error rate 0 on a branch without length against a parent entry without lengths): MAPLE_ERR_FATAL,
+ * maple_last_error names the node and the position.  Joins the traversal made ahead by maple_placement_ahead first and leaves its
+ * rows alone. */
+int maple_tree_error_probs(maple_ctx *ctx, const int32_t *nMinor /* [n], NULL = all 0 */, double minErrorProb,
+                           int32_t capLeaves, int32_t *leafNode, int64_t *outOff /* [capLeaves+1] */, int32_t *nLeaves,
+                           int64_t cap, int32_t *outPos, uint8_t *outAllele, double *outProb, int64_t *nRecords);
+
 /* ---- the search for the best root ----
  * The search of findBestRoot(tree, root), M:7730-7848 (without time trees and HnZ), on the tree of the last maple_tree_upload /
  * maple_tree_patch and the model of the last maple_set_model (MAPLE_ERR_STATE without either): the relative log-likelihood of

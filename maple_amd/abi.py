@@ -130,6 +130,8 @@ SIGNATURES = {
         "double *")),
     "maple_em_rates": ("int", ("maple_ctx *", "const int32_t *", "int", "double *", "double *", "double *", "double *")),
     "maple_tree_log_lk": ("int", ("maple_ctx *", "const int32_t *", "double *", "double *", "double *")),
+    "maple_tree_error_probs": ("int", ("maple_ctx *", "const int32_t *", "double", "int32_t", "int32_t *", "int64_t *", "int32_t *",
+        "int64_t", "int32_t *", "uint8_t *", "double *", "int64_t *")),
     "maple_tree_find_best_root": ("int", ("maple_ctx *", "const int32_t *", "const maple_root_search_params *", "int32_t *", "double *",
         "int32_t *", "double *", "int32_t", "int32_t *", "double *", "int32_t *")),
     "maple_append_batch_dev": ("int", ("maple_ctx *", "int32_t", "const int32_t *", "const int32_t *", "const uint8_t *", "const double *",

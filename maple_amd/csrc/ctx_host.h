@@ -339,7 +339,8 @@ struct maple_ctx {
     std::unique_ptr<ScratchBase> sweep;      // SweepScratch of the branch-length sweep (blen_sweep.hip)
     std::unique_ptr<ScratchBase> treelk;     // TreeLkScratch of the tree likelihood (tree_lk.hip)
     std::unique_ptr<ScratchBase> rootsearch; // RootSearchScratch of the root search (root_search.hip)
-    bool em_frames_valid = false;      // ... its per-frame mutation lists belong to the uploaded tree (dropped by maple_tree_upload)
+    std::unique_ptr<ScratchBase> errprob;    // ErrScratch of the error report (error_probs.hip)
+    bool em_frames_valid = false;     // ... its per-frame mutation lists belong to the uploaded tree (dropped by maple_tree_upload)
     bool tree_lk_valid = false;        // the post-order item list of maple_tree_log_lk belongs to the tree as it stands (dropped by
                                        // maple_tree_upload and maple_tree_patch)
     bool root_search_valid = false;    // the level lists of maple_tree_find_best_root belong to the tree as it stands (dropped likewise)

@@ -118,6 +118,26 @@ class GenomeOps:
         return tuple(float(x) for x in out[0])
 
 
+ERROR_REPORT_ALLELES = ("A", "C", "G", "T", "X")                         # allelesList, then the reference's "X" (code 4)
+
+
+def format_error_report(leaf_nodes, off, pos, allele, prob, minor_ids, node_name, names_in_tree):
+    """The text calculateErrorProbabilities writes (M:9804-9807, 9873 and its kin) for the arrays of
+    Device.error_probabilities: per leaf ``>name``; for a leaf with minor sequences their ``>name`` lines (minor_ids[v] = the ids
+    of minorSequences[v]); otherwise one ``pos\\tallele\\tprob`` line per record, prob as Python's str(float).  node_name[v] =
+    name[v], the index of v's own name in names_in_tree."""
+    off = np.asarray(off).tolist()
+    pos, allele, prob = np.asarray(pos).tolist(), np.asarray(allele).tolist(), np.asarray(prob, dtype=np.float64).tolist()
+    out = []
+    for k, v in enumerate(np.asarray(leaf_nodes).tolist()):
+        out.append(">" + names_in_tree[node_name[v]] + "\n")
+        if len(minor_ids[v]) > 0:
+            out.extend(">" + names_in_tree[i] + "\n" for i in minor_ids[v])
+        else:
+            out.extend(str(pos[i]) + "\t" + ERROR_REPORT_ALLELES[allele[i]] + "\t" + str(prob[i]) + "\n" for i in range(off[k], off[k + 1]))
+    return "".join(out)
+
+
 class TreeOps:
     """The tree-level functions of the path under the reference's own names, on a ``HostTree`` whose lists live in the
     device arena (``tree.upload(dev)`` or ``HostTree.from_mirror``).  Thin delegation: the work is in
@@ -197,6 +217,20 @@ class TreeOps:
     def expectationMaximizationCalculationRates(self, model="UNREST"):     # M:10077 (trackMutations=False)
         from .tree_host import estimate_rates
         return estimate_rates(self.dev, self.tree, model)
+
+    # M:9783 -- the reference's (tree, root, file, minErrorProb, namesInTree) with tree and root this object's; the names the
+    # reference reads off its tree are arguments here (HostTree keeps counts, not names): name[v] (None: v itself) and
+    # minorSequences[v], the ids of v's minor sequences (None: allowed when no leaf has any)
+    def calculateErrorProbabilities(self, file, minErrorProb, namesInTree, name=None, minorSequences=None):
+        t = self.tree
+        if minorSequences is None:
+            if any(t.n_minor):
+                raise ValueError("the tree has minor sequences: calculateErrorProbabilities needs their ids (minorSequences)")
+            minorSequences = [()] * t.n
+        if any(len(m) != k for m, k in zip(minorSequences, t.n_minor)):
+            raise ValueError("minorSequences does not have the tree's n_minor entries per node")
+        res = self.dev.error_probabilities(t.n_minor if any(t.n_minor) else None, minErrorProb)
+        file.write(format_error_report(*res, minorSequences, range(t.n) if name is None else name, namesInTree))
 
     def traverseTreeToOptimizeBranchLengths(self, effectivelyNon0BLen, fastPass=False):  # M:8727 (default: the Gauss-Seidel sweep)
         from .tree_host import optimize_branch_lengths, optimize_branch_lengths_fast_pass

@@ -720,6 +720,39 @@ class Device:
         self._ck(self.lib.maple_tree_log_lk(self.h, _ptr(nm), C.byref(total), C.byref(root), _ptr(node)))
         return (total.value, root.value, node) if per_node else (total.value, root.value)
 
+    def tree_error_probs(self, n_minor, min_error_prob, cap_leaves, cap):
+        """One maple_tree_error_probs call with the capacities as given (cap = 0: counted only): (status, leaf_nodes int32
+        [cap_leaves], off int64 [cap_leaves + 1], nLeaves, pos int32 [cap], allele uint8 [cap], prob float64 [cap], nRecords).  Nothing
+        is raised: the status is the library's, the message Device.last_error()."""
+        nm = None if n_minor is None else _i32(n_minor)
+        n = getattr(self, "n_nodes", 0)
+        if nm is not None and n and len(nm) != n:
+            raise MapleError(f"n_minor has {len(nm)} entries, the uploaded tree {n} nodes", MapleError.ERR_ARG)
+        leaf, off = np.full(cap_leaves, -1, np.int32), np.zeros(cap_leaves + 1, np.int64)
+        pos, al, pr = ((np.zeros(cap, np.int32), np.zeros(cap, np.uint8), np.zeros(cap)) if cap > 0 else (None, None, None))
+        n_leaves, n_rec = C.c_int32(), C.c_int64()
+        rc = self.lib.maple_tree_error_probs(self.h, _ptr(nm), float(min_error_prob), int(cap_leaves), _ptr(leaf), _ptr(off),
+                                             C.byref(n_leaves), int(cap), _ptr(pos), _ptr(al), _ptr(pr), C.byref(n_rec))
+        return rc, leaf, off, n_leaves.value, pos, al, pr, n_rec.value
+
+    def last_error(self):
+        msg = self.lib.maple_last_error(self.h)
+        return msg.decode() if msg else ""
+
+    def error_probabilities(self, n_minor=None, min_error_prob=0.01):
+        """calculateErrorProbabilities (M:9783-10020) on the uploaded tree inside the library (maple_tree_error_probs), as arrays:
+        (leaf_nodes int32 [nLeaves] in the reference's order, off int64 [nLeaves + 1], pos int32, allele uint8, prob float64) --
+        the records of leaf k are [off[k], off[k + 1]): the 1-based position, the index into allelesList or 4 for "X", and the
+        posterior probability of a sequencing error, kept where it is >= min_error_prob.  A counting call, then the full one.
+        n_minor[v] = len(minorSequences[v]), None = all 0."""
+        n = getattr(self, "n_nodes", 0)                      # (0: no tree yet, the library says so)
+        rc, _, _, n_leaves, _, _, _, n_rec = self.tree_error_probs(n_minor, min_error_prob, n, 0)
+        self._ck(rc)
+        rc, leaf, off, n_leaves, pos, al, pr, n_rec = self.tree_error_probs(n_minor, min_error_prob, n_leaves, n_rec)
+        self._ck(rc)
+        empty = (np.zeros(0, np.int32), np.zeros(0, np.uint8), np.zeros(0))
+        return (leaf, off) + (empty if pos is None else (pos, al, pr))
+
     def tree_find_best_root(self, n_minor=None, *, strictTopologyStopRules, allowedFailsTopology, thresholdLogLKtopology,
                             thresholdLogLKoptimizationTopology, thresholdLogLKconsecutivePlacement, cap_best=None, struct_size=None):
         """The search of findBestRoot (M:7730-7848) on the uploaded tree inside the library (maple_tree_find_best_root):
