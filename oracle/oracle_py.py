@@ -43,50 +43,62 @@ def build(force=False):
 
 
 def to_entries(gl, u):
-    """Reference tuple list -> OENTRY array."""
-    arr = np.zeros(len(gl), dtype=OENTRY)
+    """Reference tuple list -> OENTRY array (the fields are gathered as plain lists and stored a column at a time: lists of a
+    thousand entries are converted by the thousand in the tests on whole trees)."""
+    n = len(gl)
+    arr = np.zeros(n, dtype=OENTRY)
+    if n == 0:
+        return arr
+    d0, d1, flag, vec = [0.0] * n, [0.0] * n, [0] * n, None
     for k, e in enumerate(gl):
-        r = arr[k]
-        t = e[0]
-        r["type"] = t
-        r["x"] = e[1]
-        r["len"] = len(e)
+        t, m = e[0], len(e)
+        if m == 2:
+            continue
         if t == 6:
-            if len(e) == 4:
-                r["d0"] = e[2]
-            r["vec"] = e[-1]
-        elif t < 5 and len(e) > 2:
+            if m == 4:
+                d0[k] = e[2]
+            if vec is None:
+                vec = np.zeros((n, 4))
+            vec[k] = e[-1]
+        elif t < 5:
             if u:
-                if len(e) == 3:
+                if m == 3:
                     raise ValueError("length-3 tuple with the error model on")
-                r["d0"] = e[2]
-                if len(e) == 5:
-                    r["d1"] = e[3]
-                r["flag"] = 1 if e[-1] else 0
+                d0[k] = e[2]
+                if m == 5:
+                    d1[k] = e[3]
+                flag[k] = 1 if e[-1] else 0
             else:
-                r["d0"] = e[2]
-                if len(e) == 4:
-                    r["d1"] = e[3]
+                d0[k] = e[2]
+                if m == 4:
+                    d1[k] = e[3]
+    arr["type"] = [e[0] for e in gl]
+    arr["x"] = [e[1] for e in gl]
+    arr["len"] = [len(e) for e in gl]
+    arr["d0"], arr["d1"], arr["flag"] = d0, d1, flag
+    if vec is not None:
+        arr["vec"] = vec
     return arr
 
 
 def from_entries(arr, n, u):
     out = []
-    for k in range(n):
-        r = arr[k]
-        t, x, ln = int(r["type"]), int(r["x"]), int(r["len"])
+    a = arr[:n]
+    cols = zip(a["type"].tolist(), a["x"].tolist(), a["len"].tolist(), a["flag"].tolist(), a["d0"].tolist(), a["d1"].tolist())
+    vecs = None
+    for k, (t, x, ln, flag, d0, d1) in enumerate(cols):
         if t == 5:
             out.append((5, x))
         elif t == 6:
-            vec = [float(v) for v in r["vec"]]
-            out.append((6, x, vec) if ln == 3 else (6, x, float(r["d0"]), vec))
+            if vecs is None:
+                vecs = a["vec"].tolist()
+            out.append((6, x, vecs[k]) if ln == 3 else (6, x, d0, vecs[k]))
         elif ln == 2:
             out.append((t, x))
         elif u:
-            fl = bool(r["flag"])
-            out.append((t, x, float(r["d0"]), fl) if ln == 4 else (t, x, float(r["d0"]), float(r["d1"]), fl))
+            out.append((t, x, d0, bool(flag)) if ln == 4 else (t, x, d0, d1, bool(flag)))
         else:
-            out.append((t, x, float(r["d0"])) if ln == 3 else (t, x, float(r["d0"]), float(r["d1"])))
+            out.append((t, x, d0) if ln == 3 else (t, x, d0, d1))
     return out
 
 

@@ -23,6 +23,27 @@ def load(name):
     return _cache[name]
 
 
+def build_counting_oracle(out_dir):
+    """The oracle built with -DOMO_BRANCH_COUNTS into out_dir (the counters are listed in oracle/maple_oracle_bc.h): the library's
+    path, for Oracle(lib_path=...).  One recipe for every coverage gate."""
+    import subprocess
+    from oracle.oracle_py import HERE
+    out = os.path.join(str(out_dir), "libmaple_oracle_bc.so")
+    subprocess.check_call(["gcc", "-O2", "-std=c11", "-ffp-contract=off", "-fPIC", "-fopenmp", "-DOMO_BRANCH_COUNTS", "-shared",
+                           os.path.join(HERE, "maple_oracle.c"), os.path.join(HERE, "maple_oracle_search.c"), "-o", out, "-lm"])
+    return out
+
+
+def read_counts(lib, reset=True):
+    """{counter: hits} of a counting build of the oracle since the last reset"""
+    import ctypes as C
+    n = lib.omo_branch_counts(None, None, 0, 0)
+    vals = (C.c_longlong * n)()
+    names = (C.c_char_p * n)()
+    lib.omo_branch_counts(vals, names, n, int(reset))
+    return {names[k].decode(): int(vals[k]) for k in range(n)}
+
+
 def tup(gl):
     """JSON nested lists -> the reference's list of tuples (vectors stay lists)."""
     if gl is None:

@@ -21,6 +21,11 @@ branch:
                     position 1 and at lRef, adjacent single-site entries, a tail-less R in front of an N run or of an R with
                     a tail, a list without any R entry
   long              lists longer than the dense kernel stages (> MAPLE_QLDS entries, chunks over MAPLE_LDS_CAPW/CAPA)
+  sink_flag         (error models) three lists of a five-node tree (tests/sink_trees.py) whose new-root merges hand flagged R runs
+                    and nucleotides, several hundred of them, to findProbRoot: from a tip against N (`U && tip` of
+                    merge_step_body.inc) and from stored flags
+  sink_abandon      five-node trees, one per place where findBestRoot gives a rooting up (M:7803-7840): upVect underflows or is
+                    None, the new root's merge underflows or is None, a side given up next to a scored one
 
 `struct_corpus(mode)` gives the families of the structural operators (passGenomeListThroughBranch, shorten,
 areVectorsDifferent, rootVector, findProbRoot, isMinorSequence), one per group of counters of oracle/maple_oracle_bc.h:
@@ -392,6 +397,90 @@ def long_lists(rng, ref, u, n=6):
     return out
 
 
+def sink_case(name, k0, bk0, tipk0, k1, b1, tip1, pas, b2, tip2, expect=None):
+    """A five-node tree root -> (c1 -> (k0, k1), c2) as its three lists: lower[k0], lower[k1] = pv1 and lower[c2] = pv2, which c1
+    is handed from above over b2 = dist[c1] + dist[c2].  expect: per side what becomes of rooting above it."""
+    return dict(k0=k0, bk0=float(bk0), tipk0=bool(tipk0), pv1=k1, b1=float(b1), tip1=bool(tip1), pv2=pas, b2=float(b2), tip2=bool(tip2),
+                returnLK=True, isUpDown=False, name=name, expect=expect)
+
+
+def fam_sink_flag(rng, ref, u, n=4):
+    """Error models only.  lower[k1] and lower[c2] are N over a stretch, so upVect is; lower[k0] alternates single-site R runs and
+    nucleotides there.  Rooting above k0 merges N with them: as a tip's they come out as (type, pos, d / 2, True) (even cases), as a
+    non-tip's with stored lengths they keep their own flags, some of them False (odd cases).  Rooting above k1 first puts the
+    flags into upVect and then merges that with N.  Behind the stretch all three lists differ site by site."""
+    assert u
+    out = []
+    L = len(ref)
+    for k in range(n):
+        s = [1300, 1100, 1400, 1200][k % 4]
+        k1 = Builder(ref, u).run(5, 1, s)
+        pas = Builder(ref, u).run(5, 1, s + 20)
+        for p in range(s + 25, L - 2, 5):
+            k1.nuc(p, other(rng, int(ref[p - 1])))
+            pas.nuc(p + 1, other(rng, int(ref[p])), d0=(1e-4 if p % 2 else None), flag=False)
+        b = Builder(ref, u)
+        tip = k % 2 == 0
+        for p in range(2, L - 1, 2):
+            if tip:
+                b.nuc(p, other(rng, int(ref[p - 1])))
+            else:
+                fl = bool(p % 16 != 0)
+                b.run(4, p - 1, p - 1, d0=1e-4, flag=fl)
+                b.nuc(p, other(rng, int(ref[p - 1])), d0=(0.0 if p % 3 else 2e-5), flag=bool(p % 10 != 0))
+        out.append(sink_case(("sink_flag", k), b.done(), [1e-4, 2e-5][k % 2], tip, k1.done(), [2e-4, 1e-5][k // 2 % 2], False,
+                             pas.done(), [1e-4, 3e-4][k % 2], bool(k == 3)))
+    return out
+
+
+def fam_sink_abandon(rng, ref, u):
+    """One tree per place of abandonment.  Every side is a non-tip.  Two nodes that show different nucleotides at a site over a total
+    length of 0 have no merge (M:4757-4762); over 1e-170 they multiply the running factor by about 1e-170, and the second such
+    site of ONE merge takes it below DBL_MIN (fam_merge_underflow).  Rooting above k0 merges k1 with what comes from above (pas)
+    and the result with k0; rooting above k1 merges k0 with pas and the result with k1; c1 merges k0 with k1 and the root pas with
+    c1 -- those two must succeed.  x, y, z are three nucleotides other than the reference's, `-` is N, R the reference:
+        name                 site: k0 k1 pas     lengths k0, k1, pas     above k0          above k1
+        up_none              s:    R  x  y       1e-4    0     0         upVect None       new root None
+        new_none             s:    z  -  y       0       1e-4  0         new root None     upVect None
+        up_underflow         s, t: R  x  y       1e-4    tiny  tiny      upVect underflows new root underflows
+        new_underflow        s, t: z  -  y       tiny    1e-4  tiny      new root underfl. upVect underflows
+        sibling_scored_up    s:    x  x  y       tiny    tiny  tiny      upVect underflows scored (one tiny factor per merge)
+                             t:    y  x  y
+        sibling_scored_new   s:    z  -  y       tiny    tiny  tiny      new root underfl. scored
+                             t:    z  y  -
+    A few sites where all three agree on a nucleotide keep the lists from being empty elsewhere."""
+    out = []
+    L = len(ref)
+    tiny = 1e-170
+    specs = [("up_none", ["Rxy"], (1e-4, 0.0, 0.0), ("up_none", "new_none")),
+             ("new_none", ["z-y"], (0.0, 1e-4, 0.0), ("new_none", "up_none")),
+             ("up_underflow", ["Rxy", "Rxy"], (1e-4, tiny, tiny), ("up_underflow", "new_underflow")),
+             ("new_underflow", ["z-y", "z-y"], (tiny, 1e-4, tiny), ("new_underflow", "up_underflow")),
+             ("sibling_scored_up", ["xxy", "yxy"], (tiny, tiny, tiny), ("up_underflow", "scored")),
+             ("sibling_scored_new", ["z-y", "zy-"], (tiny, tiny, tiny), ("new_underflow", "scored"))]
+    for name, cols, (bk0, b1, b2), expect in specs:
+        ps = sorted(int(p) for p in rng.choice(np.arange(10, L - 10, 3), size=len(cols) + 6, replace=False))
+        special = [ps[2], ps[5]][:len(cols)]
+        bs = [Builder(ref, u) for _ in range(3)]
+        for p in ps:
+            r = int(ref[p - 1])
+            x = other(rng, r)
+            y = other(rng, r, (x,))
+            z = other(rng, r, (x, y))
+            if p in special:
+                for b, ch in zip(bs, cols[special.index(p)]):
+                    if ch == "-":
+                        b.run(5, p, p)
+                    elif ch != "R":
+                        b.nuc(p, dict(x=x, y=y, z=z)[ch])
+            else:                                                  # all three agree
+                for b in bs:
+                    b.nuc(p, x)
+        out.append(sink_case(("sink_abandon", name), bs[0].done(), bk0, False, bs[1].done(), b1, False, bs[2].done(), b2, False,
+                             expect=dict(k0=expect[0], k1=expect[1])))
+    return out
+
+
 def corpus(mode):
     """{family: [case dict]} of a mode (a family a mode cannot reach is left out)."""
     ref = reference()
@@ -412,6 +501,9 @@ def corpus(mode):
         "skip_edges": fam_skip_edges(rng, ref, u),
         "long": [dict(P=a, C=b, isTipC=True, bLen=1e-4) for a, b in zip(*(2 * [iter(long_lists(rng, ref, u))]))],
     }
+    if u:                                                          # (the sink families come last: the others' draws stay as they were)
+        fams["sink_flag"] = fam_sink_flag(rng, ref, u)
+    fams["sink_abandon"] = fam_sink_abandon(rng, ref, u)
     return fams
 
 

@@ -17,16 +17,13 @@ Counted, and asserted to stay at 0 (UNREACHABLE), because valid inputs cannot re
   minor_end_both      isMinorSequence's `return 0` after the loop (M:5996-5998).  found1bigger and found2bigger are tested
                       together at the end of every step, the last one included, before the loop is left (M:5977-5978).
 """
-import ctypes as C
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 import list_edges as le
-from golden_util import fixture_names, load, model_args, ref_indices, tup
-from oracle.oracle_py import HERE, Oracle
+import sink_trees as st
+from golden_util import build_counting_oracle, fixture_names, load, model_args, read_counts, ref_indices, tup
+from oracle.oracle_py import Oracle
 
 # the counters the recorded golden calls (tests/golden/calls_*.json.gz) leave at 0
 GOLDEN_ZERO = {"append_R_d1_O", "append_nuc_d1_O", "append_carry3", "merge_carry", "merge_underflow", "merge_updown_N_err_d0",
@@ -56,22 +53,13 @@ STRUCT_PREFIX = {"shorten_runs": ("shorten_",), "pass_edges": ("pass_",), "diffe
 
 @pytest.fixture(scope="module")
 def counting_lib(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("omo_bc") / "libmaple_oracle_bc.so")
-    subprocess.check_call(["gcc", "-O2", "-std=c11", "-ffp-contract=off", "-fPIC", "-fopenmp", "-DOMO_BRANCH_COUNTS", "-shared",
-                           os.path.join(HERE, "maple_oracle.c"), os.path.join(HERE, "maple_oracle_search.c"), "-o", out, "-lm"])
-    return out
-
-
-def read_counts(lib, reset=True):
-    n = lib.omo_branch_counts(None, None, 0, 0)
-    vals = (C.c_longlong * n)()
-    names = (C.c_char_p * n)()
-    lib.omo_branch_counts(vals, names, n, int(reset))
-    return {names[k].decode(): int(vals[k]) for k in range(n)}
+    return build_counting_oracle(tmp_path_factory.mktemp("omo_bc"))
 
 
 def run_case(o, fam, c):
     """One corpus case through the oracle; the merge underflow is fatal (the reference raises)."""
+    if fam.startswith("sink"):                                         # a five-node tree through the root search (test_sink_trees.py)
+        return st.oracle_root_scores(o, st.root_gadget(o, c))
     if fam.startswith("append") or fam in ("skip_edges", "long"):
         return o.appendProbNode(c["P"], c["C"], c["isTipC"], c["bLen"])
     if fam.startswith("merge"):
