@@ -31,6 +31,7 @@
 #define MAPLE_HIP_H
 #include <stdint.h>
 #include "maple_hip_root_search.h"   /* maple_root_search_params, the parameter struct of maple_tree_find_best_root */
+#include "maple_hip_mat.h"           /* maple_mut_event, maple_n_run: the records of maple_tree_mutation_events */
 
 #ifdef __cplusplus
 extern "C" {
@@ -454,6 +455,40 @@ int maple_tree_log_lk(maple_ctx *ctx, const int32_t *nMinor /* [n], NULL = all 0
 int maple_tree_error_probs(maple_ctx *ctx, const int32_t *nMinor /* [n], NULL = all 0 */, double minErrorProb,
                            int32_t capLeaves, int32_t *leafNode, int64_t *outOff /* [capLeaves+1] */, int32_t *nLeaves,
                            int64_t cap, int32_t *outPos, uint8_t *outAllele, double *outProb, int64_t *nRecords);
+
+/* ---- inferred mutation events per branch (the mutation-annotated tree) ----
+ * The record lists expectationMaximizationCalculationRates(tree, root, trackMutations=True), M:10077-10850 (--estimateMAT; without
+ * time trees and HnZ), leaves on every node, as arrays: on the tree of the last maple_tree_upload / maple_tree_patch and the model
+ * of the last maple_set_model (MAPLE_ERR_STATE without either); n = the uploaded node count.  Three streams, each laid out by node
+ * id: node v's records are [off[v], off[v+1]) in the order the reference appends them (positions ascending; within a site its
+ * i / j loop order); slots the root does not reach have empty ranges.
+ *   mut (tree.mutationsInf[v]): the substitutions inferred on the branch above v: pos = the 1-based position the reference
+ *     stores, from / to = indices into its allelesListExt, prob = the posterior probability;
+ *   ns (tree.Ns[v]): where v is uninformative: the reference's tuple (first, last) as {first, last} (also when last == first), its
+ *     bare int as {first, 0};
+ *   err (tree.errors[v]): under an error model, the probable sequencing errors of leaf v (from == 4, the reference's M:10358,
+ *     occurs only here); under a model without an error rate the stream is empty and errOff all zeros (the reference does not
+ *     create tree.errors there).
+ * Records are kept where prob > minMutProb (strict, as in the reference; its global minMutProb), but for M:10760, which appends
+ * 1.0 unconditionally.  nMinor as for maple_em_expectation (a negative one: MAPLE_ERR_ARG).
+ * Sizing: all three capacities 0 counts only (the record arrays may be NULL): the offsets and nRecords (mut, ns, err) are filled
+ * and the call returns MAPLE_OK; otherwise each capacity must hold its stream: one that is too small is MAPLE_ERR_ARG with offsets
+ * and counts valid and the needed numbers in maple_last_error.
+ * Every node the root reaches is an item of one lane (maple_amd/csrc/mat_events.hip): a non-root node with dist != 0, or a leaf
+ * under an error model, walks the (parent upper list, lower list) pair with the step of the EM walk (M:10146); every other node,
+ * the root included, walks its lower list alone for its Ns records (M:10808-10826).  The kernel runs twice: a launch that counts,
+ * three scans on the host, a launch that writes -- no float atomics, the same bytes on every call.  The parent list of a node
+ * with a mutation list is passed down through it first, into lists under an arena mark of the call's own, released on every path
+ * (MAPLE_ERR_NOMEM if the arena cannot hold them; the arena is then as it was).  A negative probability where the reference raises
+ * under rate variation (M:10293, 10336, 10368, 10422 and their kin): MAPLE_ERR_FATAL.  Joins the traversal made ahead by
+ * maple_placement_ahead first and leaves its rows alone. */
+/* maple_mut_event (16 bytes), maple_n_run (8 bytes): include/maple_hip_mat.h, included above */
+int maple_tree_mutation_events(maple_ctx *ctx, const int32_t *nMinor /* [n], NULL = all 0 */, double minMutProb,
+                               int64_t *mutOff, int64_t *nsOff, int64_t *errOff /* each [n+1] */,
+                               int64_t capMut, maple_mut_event *mut,
+                               int64_t capNs, maple_n_run *ns,
+                               int64_t capErr, maple_mut_event *err,
+                               int64_t *nRecords /* [3]: mut, ns, err */);
 
 /* ---- the search for the best root ----
  * The search of findBestRoot(tree, root), M:7730-7848 (without time trees and HnZ), on the tree of the last maple_tree_upload /

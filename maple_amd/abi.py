@@ -55,12 +55,22 @@ class MapleRootSearchParams(C.Structure):
                 ("thresholdLogLKconsecutivePlacement", C.c_double)]
 
 
+class MapleMutEvent(C.Structure):
+    _fields_ = [("pos", C.c_int32), ("from", C.c_uint8), ("to", C.c_uint8), ("zero", C.c_uint16), ("prob", C.c_double)]
+
+
+class MapleNRun(C.Structure):
+    _fields_ = [("first", C.c_int32), ("last", C.c_int32)]
+
+
 STRUCTS = {"maple_params": MapleParams, "maple_search_params": MapleSearchParams, "maple_tuning": MapleTuning,
            "maple_placement_params": MaplePlacementParams, "maple_blen_sweep_params": MapleBlenSweepParams, "maple_em_totals": MapleEmTotals}
 # include/maple_hip_root_search.h (tests/test_abi_root_search_params.py): passed by reference as a plain pointer
 ROOT_SEARCH_STRUCTS = {"maple_root_search_params": MapleRootSearchParams}
+# include/maple_hip_mat.h (tests/test_mat_fixtures.py): the records of maple_tree_mutation_events, filled through plain pointers
+MAT_STRUCTS = {"maple_mut_event": MapleMutEvent, "maple_n_run": MapleNRun}
 SCALARS = {"int": C.c_int, "int32_t": C.c_int32, "uint32_t": C.c_uint32, "int64_t": C.c_int64, "uint64_t": C.c_uint64,
-           "uint8_t": C.c_uint8, "float": C.c_float, "double": C.c_double}
+           "uint8_t": C.c_uint8, "uint16_t": C.c_uint16, "float": C.c_float, "double": C.c_double}
 
 # name: (return type, parameter types), written as the headers write them and in their order
 SIGNATURES = {
@@ -132,6 +142,8 @@ SIGNATURES = {
     "maple_tree_log_lk": ("int", ("maple_ctx *", "const int32_t *", "double *", "double *", "double *")),
     "maple_tree_error_probs": ("int", ("maple_ctx *", "const int32_t *", "double", "int32_t", "int32_t *", "int64_t *", "int32_t *",
         "int64_t", "int32_t *", "uint8_t *", "double *", "int64_t *")),
+    "maple_tree_mutation_events": ("int", ("maple_ctx *", "const int32_t *", "double", "int64_t *", "int64_t *", "int64_t *", "int64_t",
+        "maple_mut_event *", "int64_t", "maple_n_run *", "int64_t", "maple_mut_event *", "int64_t *")),
     "maple_tree_find_best_root": ("int", ("maple_ctx *", "const int32_t *", "const maple_root_search_params *", "int32_t *", "double *",
         "int32_t *", "double *", "int32_t", "int32_t *", "double *", "int32_t *")),
     "maple_append_batch_dev": ("int", ("maple_ctx *", "int32_t", "const int32_t *", "const int32_t *", "const uint8_t *", "const double *",

@@ -3,7 +3,7 @@
 // the launch attributes the scoring kernels share; and the declarations of the host functions that cross translation units
 // (hidden visibility: not part of the C ABI).  The dispatch over the three model switches, DISPATCH3, is in ctx_host.h.
 // Included by every unit with batch entry points: maple_hip.hip, append_queries.hip, placement.hip, update.hip, spr_batch.hip,
-// debug_abi.hip, blen_sweep.hip, em.hip, tree_lk.hip, root_search.hip, error_probs.hip.
+// debug_abi.hip, blen_sweep.hip, em.hip, tree_lk.hip, root_search.hip, error_probs.hip, mat_events.hip.
 #pragma once
 #include "ctx_host.h"
 

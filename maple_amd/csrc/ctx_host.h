@@ -340,6 +340,7 @@ struct maple_ctx {
     std::unique_ptr<ScratchBase> treelk;     // TreeLkScratch of the tree likelihood (tree_lk.hip)
     std::unique_ptr<ScratchBase> rootsearch; // RootSearchScratch of the root search (root_search.hip)
     std::unique_ptr<ScratchBase> errprob;    // ErrScratch of the error report (error_probs.hip)
+    std::unique_ptr<ScratchBase> matevents;  // MatScratch of the mutation events (mat_events.hip)
     bool em_frames_valid = false;     // ... its per-frame mutation lists belong to the uploaded tree (dropped by maple_tree_upload)
     bool tree_lk_valid = false;        // the post-order item list of maple_tree_log_lk belongs to the tree as it stands (dropped by
                                        // maple_tree_upload and maple_tree_patch)

@@ -1,5 +1,6 @@
 // maple_amd/csrc/em.hip -- one expectation-maximisation step for the rates of the uploaded tree
-// (expectationMaximizationCalculationRates, M:10077-10947; trackMutations=False): maple_em_expectation, maple_em_rates.
+// (expectationMaximizationCalculationRates, M:10077-10947; trackMutations=False -- the records of trackMutations=True are
+// maple_tree_mutation_events, mat_events.hip, over the same step): maple_em_expectation, maple_em_rates.
 //
 // Expectation (M:10138-10850): for every non-root branch with dist != 0, or above a leaf under an error model (M:10146), ONE LANE
 // walks the parent's upper list (upRight / upLeft of up[node], M:10150, passed down through mutList[node] first: one
@@ -87,6 +88,11 @@ __global__ __launch_bounds__(EM_BLOCK) void k_em_walk(const DevModel *__restrict
 #define OBS(p, k) atomicAdd(o.obs + (p), (unsigned long long)(k))
 #define OBSTOT(k) obsTot += (k)
 #define NEG(x) do { if (RV && (x) < 0.0) fatal = true; } while (0)
+#define MUT(i, j, x) ((void)0)         // trackMutations=False: the record hooks do nothing here (mat_events.hip feeds a sink)
+#define MUT_SURE(i, j) ((void)0)
+#define ERRREC(i, j, x) ((void)0)
+#define NS_RUN(last) ((void)0)
+#define NS_SITE() ((void)0)
         Cursor a, bb;
         a.init(list_ref(av, pl[b]));
         bb.init(list_ref(av, cl[b]));
@@ -109,6 +115,11 @@ __global__ __launch_bounds__(EM_BLOCK) void k_em_walk(const DevModel *__restrict
 #undef OBS
 #undef OBSTOT
 #undef NEG
+#undef MUT
+#undef MUT_SURE
+#undef ERRREC
+#undef NS_RUN
+#undef NS_SITE
         if (obsTot != 0) atomicAdd(o.obs + (lRef + 1), (unsigned long long)obsTot);
         if (fatal) *o.fatal = 1;
     }
@@ -279,10 +290,14 @@ int expectation(maple_ctx *c, const int32_t *nMinorArr, EmHost &H)
     TRY(h2d(c, S.d_frame, frame.data(), (size_t)nB));
     TRY(h2d(c, S.d_dist, dist.data(), (size_t)nB));
     EmOut o{S.d_partials.p, S.d_tables.p, S.d_tables.p + 4 * L1, S.d_tables.p + 5 * L1, S.d_tables.p + 6 * L1, S.d_obs.p, S.d_fatal.p};
+    hipEvent_t e0, e1;                 // (maple_timing_*: the walk's own time, what tools/mutation_events_stats.py compares with)
+    TRY(ev_pair(c, &e0, &e1, MAPLE_K_OTHER, (double)nB, 0.0));
+    HIPCK(c, hipEventRecord(e0, c->stream));
     DISPATCH3(c, k_em_walk, <<<dim3(blocks), dim3(EM_BLOCK), 0, c->stream>>>(c->d_model.p, view(c), nB, S.d_pl.p, S.d_cl.p, S.d_dist.p,
                                                                             S.d_leafMinor.p, S.d_frame.p, S.d_fm.p, S.d_fmOff.p,
                                                                             S.d_refIdx.p, o));
     HIPCK(c, hipGetLastError());
+    HIPCK(c, hipEventRecord(e1, c->stream));
     std::vector<double> partials((size_t)blocks * EM_NACC), tables(nTab);
     std::vector<unsigned long long> obs(L1 + 1);
     int32_t fatal = 0;

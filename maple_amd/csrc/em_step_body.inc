@@ -8,6 +8,10 @@
 //   WTS(i, x) waitingTimesSites[pos][i] += x; WTS_AT(p, i, x); CS(x) countsSites[pos] += x; TN(p, x) trackingNs[p] += x;
 //   ECS(x) errorCountSites[pos] += x; OBS(p, k) observedNucsSites[p] += k; OBSTOT(k) observedTotNucsSites += k
 //   NEG(x) the reference's "if x < 0.0: raise" under rate variation.
+// and the hooks at the places where the reference, under trackMutations, appends a record (empty in k_em_walk; the sink of
+// k_mat_walk, mat_events.hip):
+//   MUT(i, j, x) mutationsInf[node].append((i, pos+1, j, x)) if x > minMutProb; MUT_SURE(i, j) the unconditional one of M:10760;
+//   ERRREC(i, j, x) errors[node].append((i, pos+1, j, x)) if x > minMutProb; NS_RUN(last) M:10180-10182; NS_SITE() M:10256 / 10432.
 // The per-site macros do nothing where the model has no such table.
 {
     while (iFm < nFm && fm[iFm].x < pos) iFm++;                          // M:10166-10167
@@ -18,6 +22,7 @@
             else OBSTOT(-(long long)(end - pos) * (1 + nMinor));
         }
         TN(pos, -dist);
+        NS_RUN(e2.pos);
         pos = end;
         TN(pos, dist);
         if (U && SS && leaf) OBS(pos, (long long)(1 + nMinor));
@@ -57,6 +62,7 @@
                     double normalization = 0.0;
                     WTS(refN, -totLen1);
                     if (e2.type == 6) {
+                        if (leaf) NS_SITE();                             // M:10255-10256
                         if (leaf && U) {                                 // M:10257-10293
                             const double errorRate = c.err(pos);
                             double noMutProb = 0.0, mutProb = 0.0, errorProb = 0.0;
@@ -114,6 +120,7 @@
                                         WT(i, (totLen1 / 2) * prob);
                                         WT(j, (totLen1 / 2) * prob);
                                         CNT(i, j, prob);
+                                        MUT(i, j, prob);
                                         WTS(i, (totLen1 / 2) * prob);
                                         WTS(j, (totLen1 / 2) * prob);
                                         CS(prob);
@@ -134,6 +141,7 @@
                             noMutProb = noMutProb / normalization;
                             mutProb = mutProb / normalization;
                             ERRC(errorProb);
+                            ERRREC(4, i2, errorProb);
                             ECS(errorProb);
                             WT(i2, totLen1 * noMutProb);
                             WT(i2, (totLen1 / 2) * mutProb);
@@ -147,6 +155,7 @@
                                     const double probErr = v1[i] * errorRate * 0.33333 / normalization;
                                     WT(i, totLen1 * (probErr + prob / 2));
                                     CNT(i, i2, prob);
+                                    MUT(i, i2, prob);
                                     WTS(i, totLen1 * (probErr + prob / 2));
                                 }
                         } else {                                         // M:10382-10422
@@ -170,6 +179,7 @@
                                     WT(i, (totLen1 / 2) * prob);
                                     WT(i2, (totLen1 / 2) * prob);
                                     CNT(i, i2, prob);
+                                    MUT(i, i2, prob);
                                     WTS(i, (totLen1 / 2) * prob);
                                     WTS(i2, (totLen1 / 2) * prob);
                                     CS(prob);
@@ -182,6 +192,7 @@
             } else {                                                     // the parent side shows a nucleotide, M:10424-10788
                 const int i1 = (e1.type == 4) ? e2.ref : e1.type;
                 if (e2.type == 6) {                                      // ... the child an O vector, M:10430-10676
+                    if (leaf) NS_SITE();                                 // M:10431-10432
                     if (v2[i1] > 0.1) {                                  // the parent's nucleotide is possible: nothing happened
                         WT(i1, totLen1);
                         WTS(refN, -totLen1);
@@ -308,6 +319,7 @@
                                             WT(i, (totLen1 / 2) * tot3);
                                             WT(j, (totLen1 / 2) * tot3);
                                             CNT(i, j, tot3);
+                                            if (!leaf) MUT(i1, j, tot3); // (sic: i1 == i here, M:10619-10620)
                                             WTS(i, (totLen1 / 2) * tot3);
                                             WTS(j, (totLen1 / 2) * tot3);
                                             CS(tot3);
@@ -343,6 +355,7 @@
                                     WT(i1, (totLen1 / 2) * prob);
                                     WT(i, (totLen1 / 2) * prob);
                                     CNT(i1, i, prob);
+                                    if (!leaf) MUT(i1, i, prob);         // M:10669-10670
                                     WTS(i1, (totLen1 / 2) * prob);
                                     WTS(i, (totLen1 / 2) * prob);
                                     CS(prob);
@@ -375,6 +388,8 @@
                             WT(i1, totLen1 * (errorProb + mutProb / 2));
                             WT(i2, (totLen1 * mutProb / 2));
                             CNT(i1, i2, mutProb);
+                            MUT(i1, i2, mutProb);
+                            ERRREC(i1, i2, errorProb);
                             ERRC(errorProb);
                             ECS(errorProb);
                         } else {                                         // across the root, M:10722-10747
@@ -388,6 +403,8 @@
                             WT(i1, totLen1 * (mutprob1 / 2 + errorProb));
                             WT(i2, totLen1 * (mutprob2 + mutprob1 / 2));
                             CNT(i1, i2, mutprob1);
+                            MUT(i1, i2, mutprob1);
+                            ERRREC(i1, i2, errorProb);
                             ERRC(errorProb);
                             ECS(errorProb);
                             WTS(refN, -totLen1);
@@ -405,6 +422,7 @@
                             WT(i1, (totLen1 / 2));
                             WT(i2, (totLen1 / 2));
                             CNT(i1, i2, 1.0);
+                            MUT_SURE(i1, i2);
                         } else {                                         // across the root
                             double noMutProb1 = 1.0 + q(i1, i1) * e1.d0;
                             if (noMutProb1 < 0) noMutProb1 = 0.25;
@@ -418,6 +436,7 @@
                             WT(i1, (totLen1 / 2) * prob1);
                             WT(i2, (totLen1 / 2) * prob1);
                             CNT(i1, i2, prob1);
+                            MUT(i1, i2, prob1);
                             WT(i2, totLen1 * prob2);
                             WTS(refN, -totLen1);
                             WTS(i1, (totLen1 / 2) * prob1);

@@ -138,6 +138,66 @@ def format_error_report(leaf_nodes, off, pos, allele, prob, minor_ids, node_name
     return "".join(out)
 
 
+MAT_ALLELES = ("A", "C", "G", "T", "?")                                    # allelesListExt (M:3661)
+
+
+def format_root_state(root_vect, min_mut_prob):
+    """The root's ``rootState={...}`` of stringForNode (M:2750-2781) from rootVector(probVect[root], False, isTip, ...) as a list
+    of the reference's tuples (GenomeOps.rootVector / Device.download): an N run as ``N<first>-<last>``, a nucleotide as
+    ``<allele><pos>:1.0``, an O entry as its alleles with a value above min_mut_prob, values as Python's str(float)."""
+    out, pos, first = "rootState={", 0, True
+    for e in root_vect:
+        if e[0] != 4:
+            if not first:
+                out += ","
+            first = False
+        if e[0] == 5:
+            out += "N" + str(pos + 1) + "-" + str(e[1])
+            pos = e[1]
+        elif e[0] == 6:
+            out += ",".join(MAT_ALLELES[i] + str(pos + 1) + ":" + str(float(e[-1][i])) for i in range(4) if e[-1][i] > min_mut_prob)
+            pos += 1
+        elif e[0] < 4:
+            out += MAT_ALLELES[e[0]] + str(pos + 1) + ":1.0"
+            pos += 1
+        else:
+            pos = e[1]
+    return out + "}"
+
+
+def format_mat_annotation(mut_off, ns_off, err_off, mut, ns, err, *, root, up, children, dist, errors_on, effectivelyNon0BLen,
+                          supportFor0Branches=False, root_state=None):
+    """Per node, what the reference's stringForNode(tree, v, "", dist[v], estimateMAT=True, networkOutput=False,
+    aBayesPlusOn=False) returns (M:2673-2809) for the arrays of Device.mutation_events: the
+    ``[&mutationsInf={A123C:0.98,...},Ns={5,10-20},errors={...}]`` block under the conditions of M:2706 and M:2719 (a non-root node
+    whose dist is above effectivelyNon0BLen, or supportFor0Branches, or an error model -- errors_on; then dist non-zero, or an error
+    model, or a leaf), the root's ``[&rootState={...}]`` (root_state: format_root_state's text, None: left out), the empty string
+    where the reference writes nothing and for slots the root does not reach.  Probabilities go through Python's str(float)."""
+    mut_off, ns_off, err_off = (np.asarray(x).tolist() for x in (mut_off, ns_off, err_off))
+
+    def events(a, lo, hi):
+        pos, fr, to, pr = a["pos"][lo:hi].tolist(), a["from"][lo:hi].tolist(), a["to"][lo:hi].tolist(), a["prob"][lo:hi].tolist()
+        return ",".join(MAT_ALLELES[f] + str(p) + MAT_ALLELES[t] + ":" + str(x) for p, f, t, x in zip(pos, fr, to, pr))
+
+    out = []
+    for v in range(len(up)):
+        strings = []
+        d = dist[v] or 0.0
+        if up[v] is not None and up[v] >= 0:
+            if (d > effectivelyNon0BLen or supportFor0Branches or errors_on) and (d or errors_on or not len(children[v])):
+                if mut_off[v + 1] > mut_off[v]:
+                    strings.append("mutationsInf={" + events(mut, mut_off[v], mut_off[v + 1]) + "}")
+                if ns_off[v + 1] > ns_off[v]:
+                    first, last = ns["first"][ns_off[v]:ns_off[v + 1]].tolist(), ns["last"][ns_off[v]:ns_off[v + 1]].tolist()
+                    strings.append("Ns={" + ",".join(str(a) if b == 0 else str(a) + "-" + str(b) for a, b in zip(first, last)) + "}")
+                if errors_on and not len(children[v]) and err_off[v + 1] > err_off[v]:
+                    strings.append("errors={" + events(err, err_off[v], err_off[v + 1]) + "}")
+        elif v == root and root_state is not None:               # (another slot without a parent is one the root does not reach)
+            strings.append(root_state)
+        out.append("[&" + ",".join(strings) + "]" if strings else "")
+    return out
+
+
 class TreeOps:
     """The tree-level functions of the path under the reference's own names, on a ``HostTree`` whose lists live in the
     device arena (``tree.upload(dev)`` or ``HostTree.from_mirror``).  Thin delegation: the work is in
@@ -231,6 +291,23 @@ class TreeOps:
             raise ValueError("minorSequences does not have the tree's n_minor entries per node")
         res = self.dev.error_probabilities(t.n_minor if any(t.n_minor) else None, minErrorProb)
         file.write(format_error_report(*res, minorSequences, range(t.n) if name is None else name, namesInTree))
+
+    # --estimateMAT (M:12529-12532, 12601-12606): expectationMaximizationCalculationRates(tree, root, trackMutations=True) and then,
+    # per node, the annotation stringForNode writes into the Nexus tree; minMutProb is the reference's global of that name
+    def estimateMAT(self, minMutProb, effectivelyNon0BLen, supportFor0Branches=False):
+        t, d = self.tree, self.dev
+        res = d.mutation_events(t.n_minor if any(t.n_minor) else None, minMutProb)
+        root = t.root
+        mark = d.mark()
+        try:                                                             # rootVector(probVect[root], False, isTip, tree, root), M:2754
+            is_tip = len(t.children[root]) == 0 and t.n_minor[root] == 0
+            path = [int(t.id_mut[root])] if t.id_mut[root] >= 0 else []
+            root_vect = d.download(d.root_vector_batch([int(t.id_lower[root])], [0.0], [is_tip], [path]))[0]
+        finally:
+            d.release(mark)
+        return format_mat_annotation(*res, root=root, up=t.up, children=t.children, dist=t.dist, errors_on=bool(d.u),
+                                     effectivelyNon0BLen=effectivelyNon0BLen, supportFor0Branches=supportFor0Branches,
+                                     root_state=format_root_state(root_vect, minMutProb))
 
     def traverseTreeToOptimizeBranchLengths(self, effectivelyNon0BLen, fastPass=False):  # M:8727 (default: the Gauss-Seidel sweep)
         from .tree_host import optimize_branch_lengths, optimize_branch_lengths_fast_pass

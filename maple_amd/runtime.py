@@ -23,6 +23,9 @@ EXPORTS, DEBUG_EXPORTS = list(SIGNATURES), list(DEBUG_SIGNATURES)
 LIB_PATH_DEBUG = os.path.join(HERE, "libmaple_hip_debug.so")
 
 EM_MODELS = {"UNREST": 0, "GTR": 1}
+# the records of maple_tree_mutation_events as numpy sees them: maple_mut_event / maple_n_run of include/maple_hip_mat.h
+MUT_EVENT_DTYPE = np.dtype([("pos", "<i4"), ("from", "u1"), ("to", "u1"), ("zero", "<u2"), ("prob", "<f8")], align=True)
+N_RUN_DTYPE = np.dtype([("first", "<i4"), ("last", "<i4")], align=True)
 
 _lib = None
 _lib_debug = None
@@ -752,6 +755,36 @@ class Device:
         self._ck(rc)
         empty = (np.zeros(0, np.int32), np.zeros(0, np.uint8), np.zeros(0))
         return (leaf, off) + (empty if pos is None else (pos, al, pr))
+
+    def tree_mutation_events(self, n_minor, min_mut_prob, cap_mut, cap_ns, cap_err):
+        """One maple_tree_mutation_events call with the capacities as given (all 0: counted only): (status, mutOff, nsOff, errOff
+        int64 [n + 1], mut MUT_EVENT_DTYPE [cap_mut], ns N_RUN_DTYPE [cap_ns], err MUT_EVENT_DTYPE [cap_err], nRecords int64 [3]);
+        an array of capacity 0 is None.  Nothing is raised: the status is the library's, the message Device.last_error()."""
+        nm = None if n_minor is None else _i32(n_minor)
+        n = getattr(self, "n_nodes", 0)
+        if nm is not None and n and len(nm) != n:
+            raise MapleError(f"n_minor has {len(nm)} entries, the uploaded tree {n} nodes", MapleError.ERR_ARG)
+        offs = [np.zeros(n + 1, np.int64) for _ in range(3)]
+        mut = np.zeros(cap_mut, MUT_EVENT_DTYPE) if cap_mut > 0 else None
+        ns = np.zeros(cap_ns, N_RUN_DTYPE) if cap_ns > 0 else None
+        err = np.zeros(cap_err, MUT_EVENT_DTYPE) if cap_err > 0 else None
+        n_rec = np.zeros(3, np.int64)
+        rc = self.lib.maple_tree_mutation_events(self.h, _ptr(nm), float(min_mut_prob), _ptr(offs[0]), _ptr(offs[1]), _ptr(offs[2]),
+                                                 int(cap_mut), _ptr(mut), int(cap_ns), _ptr(ns), int(cap_err), _ptr(err), _ptr(n_rec))
+        return rc, offs[0], offs[1], offs[2], mut, ns, err, n_rec
+
+    def mutation_events(self, n_minor=None, min_mut_prob=0.01):
+        """The records expectationMaximizationCalculationRates(tree, root, trackMutations=True) leaves on the nodes (M:10077-10850,
+        --estimateMAT) for the uploaded tree, inside the library (maple_tree_mutation_events), as arrays: (mutOff, nsOff, errOff,
+        mut, ns, err) -- node v's records are [off[v], off[v + 1]) of its stream; mut / err: MUT_EVENT_DTYPE (pos 1-based, from / to
+        indices into allelesListExt, prob kept where > min_mut_prob), ns: N_RUN_DTYPE (last == 0: the reference's bare int).  A
+        counting call, then the full one.  n_minor[v] = len(minorSequences[v]), None = all 0."""
+        rc, _, _, _, _, _, _, n_rec = self.tree_mutation_events(n_minor, min_mut_prob, 0, 0, 0)
+        self._ck(rc)
+        rc, mo, no, eo, mut, ns, err, _ = self.tree_mutation_events(n_minor, min_mut_prob, *(int(x) for x in n_rec))
+        self._ck(rc)
+        return (mo, no, eo, np.zeros(0, MUT_EVENT_DTYPE) if mut is None else mut, np.zeros(0, N_RUN_DTYPE) if ns is None else ns,
+                np.zeros(0, MUT_EVENT_DTYPE) if err is None else err)
 
     def tree_find_best_root(self, n_minor=None, *, strictTopologyStopRules, allowedFailsTopology, thresholdLogLKtopology,
                             thresholdLogLKoptimizationTopology, thresholdLogLKconsecutivePlacement, cap_best=None, struct_size=None):
