@@ -31,6 +31,16 @@ int maple_debug_frontier_levels(maple_ctx *ctx, int32_t cap, int64_t *itemsUpdat
 int maple_debug_frontier_wave_paths(maple_ctx *ctx, int64_t *counts, int32_t cap, float *levelSlowestMs, int32_t *levelSlowestSlot,
                                     double *slots, int32_t *profiled);
 
+/* The searches that pass handed to the one-lane-per-search kernel (k_spr_search), so that a test of the frontier tier can tell
+ * that the tier itself answered.  *searchesHandedBack: all of them, whatever the cause (a pool or a scratch slab too small
+ * included).  reasons[8]: those the exact walk (k_fr_replay) and the whole-tree replay (k_fr_replay_wide) give a reason for --
+ * [1] a merge within tolerance of the stop rule, [2] a list re-expressed through a reference branch from one that shorten()
+ * (M:7087) changed, [3] a fifth shortened list, [4] the search's own first list shortened, [5] a marked list without a layout,
+ * [0] other; whole-tree searches: [6] a short list, scan slots or a marked item list, [7] a scanned branch whose list shorten()
+ * would change.  When maple_spr_search_batch runs the tier more than once (whole-tree searches found by their budget), this is
+ * the last pass. */
+int maple_debug_frontier_handbacks(maple_ctx *ctx, int64_t *reasons, int64_t *searchesHandedBack);
+
 /* appendProbNode for n (parent list, child list) pairs with ONE WAVEFRONT per pair (maple_amd/csrc/wave_dev.h: the walk cut
  * along its merge path, the factors of all steps at once, the running product in walk order): the same results as
  * maple_append_batch bit for bit; *ms (optional) = kernel time.  A test and timing aid. */

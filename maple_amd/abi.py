@@ -166,6 +166,7 @@ SIGNATURES = {
 DEBUG_SIGNATURES = {
     "maple_debug_frontier_levels": ("int", ("maple_ctx *", "int32_t", "int64_t *", "int64_t *", "float *", "float *", "int32_t *", "int64_t *",
         "int64_t *")),
+    "maple_debug_frontier_handbacks": ("int", ("maple_ctx *", "int64_t *", "int64_t *")),
     "maple_debug_frontier_wave_paths": ("int", ("maple_ctx *", "int64_t *", "int32_t", "float *", "int32_t *", "double *", "int32_t *")),
     "maple_debug_wave_append_batch": ("int", ("maple_ctx *", "int32_t", "const int32_t *", "const int32_t *", "const uint8_t *", "const double *",
         "double *", "float *")),

@@ -230,6 +230,16 @@ extern "C" int maple_debug_frontier_wave_paths(maple_ctx *c, int64_t *counts, in
     return rc;
 }
 
+extern "C" int maple_debug_frontier_handbacks(maple_ctx *c, int64_t *reasons, int64_t *searchesHandedBack)
+{
+    if (!c || !reasons || !searchesHandedBack) return MAPLE_ERR_ARG;
+    long long r[8] = {}, n = 0;
+    const int rc = frontier_handbacks(c, r, &n);
+    for (int k = 0; k < 8; k++) reasons[k] = r[k];
+    *searchesHandedBack = n;
+    return rc;
+}
+
 // ---- passGenomeListThroughBranch of a removed list as the frontier tier of the SPR search runs it (frontier_dev.h) ---------------
 // The tier's two forms -- one lane per item (fpass_removed: fpass_store + shorten_would_merge) and one wavefront per item
 // (wave_pass with `removed` set) -- are reached in the product only from inside a search on a tree with MAT local references.

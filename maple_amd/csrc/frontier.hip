@@ -1116,6 +1116,7 @@ struct FrontierScratch : ScratchBase {
     // ... and what its wavefront-wide kernels did (frontier_wave_paths): FCtr::wavePath; with MAPLE_SPR_PROFILE the dbgW slots
     // (count, ticks, slowest) and the slowest wavefront-wide item of every level
     unsigned long long lastWavePath[FR_WP_N] = {};
+    long long lastFbReason[8] = {}, lastHandedBack = 0;   // ... and what it handed to the one-lane kernel (frontier_handbacks)
     std::vector<unsigned long long> lastProfW, lastProfLvl;
     plan::FrontierNeeds need;                        // what the last call that counts asked of the pools (plan::remember_frontier)
     FPools lastPools{};
@@ -1489,7 +1490,9 @@ int frontier_search(maple_ctx *c, const SearchParams &P, int m, const int32_t *n
         const double meanCand = c->n_scored ? c->scored_bytes_total / c->n_scored : 0.0;
         double units = 0.0, bytes = 0.0;
         double unitsW = 0.0, bytesW = 0.0;
+        F.lastHandedBack = 0;
         for (int k = 0; k < m; k++) {
+            F.lastHandedBack += hostOut[k].status == FR_STATUS_FALLBACK;    // (for frontier_handbacks)
             if (hostOut[k].status != 0 && hostOut[k].status != -1) continue;
             if (anyWide && wide->rowOf[k] >= 0) {                           // replayed over its score row: 8 B per placement + its list
                 const int32_t l = c->h_tree_lower[nodes[k]];
@@ -1543,6 +1546,7 @@ int frontier_search(maple_ctx *c, const SearchParams &P, int m, const int32_t *n
     F.lastU = std::min((long long)hc.usedU, fp.capU); F.lastC = std::min((long long)hc.usedC, fp.capCC);
     F.lastR = std::min((long long)hc.usedR, fp.capC - fp.capCC); F.lastPools = fp;
     std::copy(hc.wavePath, hc.wavePath + FR_WP_N, F.lastWavePath);
+    std::copy(hc.fbReason, hc.fbReason + 8, F.lastFbReason);
 #ifdef MAPLE_SPR_PROFILE
     F.lastProfW.assign(hc.dbgWCnt, hc.dbgWCnt + 8);
     F.lastProfW.insert(F.lastProfW.end(), hc.dbgWT, hc.dbgWT + 8);
@@ -1609,6 +1613,17 @@ int frontier_wave_paths(maple_ctx *c, long long *counts, int cap, float *lvlMs, 
         const unsigned long long v = l < (int)F->lastProfLvl.size() ? F->lastProfLvl[l] : 0ull;
         lvlMs[l] = (float)((v >> 4) * 1e-5); lvlSlot[l] = (int)(v & 15ull);
     }
+    return MAPLE_OK;
+}
+
+// The searches the last frontier_search handed to the one-lane-per-search kernel: *searches of them in all (pools and scratch
+// included), reasons[8] = FCtr::fbReason, those the exact walk and the whole-tree replay gave a reason for.
+int frontier_handbacks(maple_ctx *c, long long *reasons, long long *searches)
+{
+    FrontierScratch *F = static_cast<FrontierScratch *>(c->frontier.get());
+    if (!F) return fail(c, MAPLE_ERR_STATE, "no frontier search to report on");
+    std::copy(F->lastFbReason, F->lastFbReason + 8, reasons);
+    *searches = F->lastHandedBack;
     return MAPLE_OK;
 }
 

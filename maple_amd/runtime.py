@@ -664,6 +664,17 @@ class Device:
             return paths, None, None
         return paths, slots.reshape(3, 8).T.copy(), (ms, slot)
 
+    HANDBACK_REASONS = ("other", "merge_within_tolerance", "passed_from_shortened", "fifth_shortened_list", "own_list_shortened",
+                        "marked_without_layout", "wide_short_list_or_slots", "wide_scanned_list_shortened")
+
+    def frontier_handbacks(self):
+        """Of the last frontier-tier pass (maple_debug_frontier_handbacks): (the searches it handed to the one-lane kernel, a dict
+        of those that were given a reason, by HANDBACK_REASONS)."""
+        reasons = np.zeros(8, np.int64)
+        n = C.c_int64()
+        self._ck(self.lib.maple_debug_frontier_handbacks(self.h, _ptr(reasons), C.byref(n)))
+        return int(n.value), dict(zip(self.HANDBACK_REASONS, reasons.tolist()))
+
     def tree_rebuild_lists(self, root, up, c0, c1, tip, mut, dist, lower, bump_len=0.0):
         """reCalculateAllGenomeLists (M:6013-6347) with the level loop inside the library (maple_tree_rebuild_lists): returns
         (lower, upRight, upLeft, totUp, bad) -- new id columns, ``dist`` (float64, contiguous) updated in place when bump_len > 0,

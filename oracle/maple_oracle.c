@@ -22,7 +22,8 @@
 #include "maple_oracle_bc.h"
 #define OMO_BC_NAME_(e, n) n,
 static const char *const omo_bc_names[BC_N] = {OMO_BC_LIST(OMO_BC_NAME_)};
-long long omo_bc[BC_N];
+static const char *const omo_bc_search_names[BC_ALL_N - BC_N] = {OMO_BC_SEARCH_LIST(OMO_BC_NAME_)};
+long long omo_bc[BC_ALL_N];
 /* copies up to n counters into out (and their names into names, if given), zeroes them when reset; returns how many exist */
 int omo_branch_counts(long long *out, const char **names, int n, int reset)
 {
@@ -32,6 +33,16 @@ int omo_branch_counts(long long *out, const char **names, int n, int reset)
         if (reset) __atomic_store_n(&omo_bc[k], 0, __ATOMIC_RELAXED);
     }
     return BC_N;
+}
+/* the same for the counters of the SPR search (OMO_BC_SEARCH_LIST) */
+int omo_search_branch_counts(long long *out, const char **names, int n, int reset)
+{
+    for (int k = 0; k < BC_ALL_N - BC_N && k < n; k++) {
+        if (out) out[k] = __atomic_load_n(&omo_bc[BC_N + k], __ATOMIC_RELAXED);
+        if (names) names[k] = omo_bc_search_names[k];
+        if (reset) __atomic_store_n(&omo_bc[BC_N + k], 0, __ATOMIC_RELAXED);
+    }
+    return BC_ALL_N - BC_N;
 }
 #else
 #define BC(k) ((void)0)

@@ -1,7 +1,8 @@
 /*
  * oracle/maple_oracle_bc.h -- TEST INFRASTRUCTURE ONLY: the branch counters of the coverage gate
- * (tests/test_list_edges_coverage.py).  Included by maple_oracle.c and maple_oracle_search.c only under
- * -DOMO_BRANCH_COUNTS; the default build, the one the golden tests pin, never sees this file.
+ * (tests/test_list_edges_coverage.py; the search's own, at the end, are those of tests/test_search_trees.py).  Included by
+ * maple_oracle.c and maple_oracle_search.c only under -DOMO_BRANCH_COUNTS; the default build, the one the golden tests pin, never
+ * sees this file.
  *
  * Each counter counts one rarely taken branch of an operator.  OMO_BC_PASS(E, name) makes two counters, E_DOWN and E_UP
  * (= E_DOWN + 1), one per direction of passGenomeListThroughBranch: BC(E_DOWN + dirIsUp).
@@ -103,9 +104,46 @@
     X(BC_MINOR_END_EQUAL, "minor_end_equal")                                                                                 \
     X(BC_MINOR_END_BOTH, "minor_end_both")                 /* 0 after the loop */
 
+/* The arms of the SPR regraft search (omo_findBestParentTopology, omo_sprWorker), the counters of tests/test_search_trees.py.
+ * They follow BC_N in the same array and are read through omo_search_branch_counts, so that omo_branch_counts lists the
+ * operators' counters only.  OMO_BC_MERGE(X, E, name) makes two counters for a merge of the search that has no result: E, the
+ * reference's "the merge is None" (mergeVectors itself returned None on two lists), and E_ABSENT (= E + 1), an input list the
+ * tree does not have. */
+#define OMO_BC_MERGE(X, E, name) X(E, "search_" name "_none") X(E##_ABSENT, "search_" name "_absent")
+
+#define OMO_BC_SEARCH_LIST(X) \
+    X(BC_SRCH_SEED_ROOT_SIB_INNER, "search_seed_root_sibling_inner") /* the pruned node hangs on the root, its sibling has children, M:6916-6957 */ \
+    X(BC_SRCH_SEED_ROOT_SIB_LEAF, "search_seed_root_sibling_leaf")   /* ... its sibling is a leaf: nothing to search */            \
+    OMO_BC_MERGE(X, BC_SRCH_DOWN_MID, "down_mid")          /* going down, updating: midTot, M:7037-7044 */                       \
+    X(BC_SRCH_DOWN_STOP, "search_down_stop")               /* going down: the stop rule, midTot is the stored probVectTotUp */    \
+    X(BC_SRCH_SHORTEN_OWN, "search_shorten_own")           /* M:7087 changes the removed list: the search's own first list */     \
+    X(BC_SRCH_SHORTEN_PASSED, "search_shorten_passed")     /* ... a list re-expressed through a reference branch */              \
+    OMO_BC_MERGE(X, BC_SRCH_DOWN_VUP, "down_vup")          /* going down, updating: the child's vectUp; the child is not pushed */ \
+    OMO_BC_MERGE(X, BC_SRCH_UP_BOTTOM, "up_bottom")        /* crawling up, updating: midBottom, M:7170-7178 */                   \
+    X(BC_SRCH_UP_TOTUP_ON_THE_SPOT, "search_up_totup_on_the_spot") /* the node has no probVectTotUp: made on the spot, M:7198-7200 */ \
+    OMO_BC_MERGE(X, BC_SRCH_UP_MID, "up_mid")              /* crawling up, updating: midTot */                                   \
+    X(BC_SRCH_UP_STOP, "search_up_stop")                   /* crawling up: the stop rule */                                      \
+    OMO_BC_MERGE(X, BC_SRCH_UP_VUP, "up_vup")              /* crawling up: the sibling's vectUp (absent: also the cached list) */  \
+    OMO_BC_MERGE(X, BC_SRCH_UP_BOTTOM_LATE, "up_bottom_late") /* crawling up: midBottom made late, over a short branch */         \
+    X(BC_SRCH_ROOT_CROSS_UPDATING, "search_root_cross_updating")   /* over the root into its other child, rootVector, M:7392-7420 */ \
+    X(BC_SRCH_ROOT_CROSS_CACHED, "search_root_cross_cached")                                                                    \
+    X(BC_SRCH_SCORE_MINUS_INF, "search_score_minus_inf")   /* a placement scored -inf */                                         \
+    X(BC_SRCH_REFINE_NO_LIST, "search_refine_no_list")     /* refinement: a record without up, down or mid list; the reference raises */ \
+    OMO_BC_MERGE(X, BC_SRCH_REFINE_LOWER, "refine_lower")  /* refinement: midLower; raises */                                    \
+    X(BC_SRCH_REFINE_TOP_RETRY, "search_refine_top_retry") /* refinement: midTop None, retried with top = defaultBLen * 0.1 */    \
+    X(BC_SRCH_REFINE_TOP_NONE, "search_refine_top_none")   /* ... None again; raises */                                          \
+    X(BC_SRCH_REFINE_NEWMID_NONE, "search_refine_newmid_none") /* refinement: newMid None; raises */                             \
+    X(BC_SRCH_STATUS_MINUS_1, "search_status_minus_1")     /* the worker: the search itself raised */                            \
+    X(BC_SRCH_STATUS_2, "search_status_2")                 /* the worker: not searched, a zero-length branch with a good cost */   \
+    X(BC_SRCH_VETO_PARENT, "search_veto_parent")           /* the accept rule, M:9681-9700: bestNode is the parent */             \
+    X(BC_SRCH_CHAIN_STEP, "search_chain_step")             /* ... one step up the chain of zero-length branches */               \
+    X(BC_SRCH_VETO_CHAIN_TOP, "search_veto_chain_top")     /* ... bestNode is the chain's top and blen[1] == 0 */                 \
+    X(BC_SRCH_VETO_SIBLING, "search_veto_sibling")         /* ... bestNode is the sibling */                                     \
+    X(BC_SRCH_VETO_BELOW_SIBLING, "search_veto_below_sibling") /* ... bestNode hangs on the sibling and blen[0] == 0 */
+
 #define OMO_BC_ENUM_(e, n) e,
-enum { OMO_BC_LIST(OMO_BC_ENUM_) BC_N };
-extern long long omo_bc[BC_N];
+enum { OMO_BC_LIST(OMO_BC_ENUM_) BC_N, BC_SEARCH_BEFORE_ = BC_N - 1, OMO_BC_SEARCH_LIST(OMO_BC_ENUM_) BC_ALL_N };
+extern long long omo_bc[BC_ALL_N];
 #define BC(k) __atomic_fetch_add(&omo_bc[k], 1, __ATOMIC_RELAXED)
 
 #endif

@@ -14,9 +14,13 @@
 #include <string.h>
 
 #ifdef OMO_BRANCH_COUNTS
-#include "maple_oracle_bc.h"        /* the counters of tests/test_list_edges_coverage.py; the default build has none */
+#include "maple_oracle_bc.h"        /* the counters of tests/test_list_edges_coverage.py and test_search_trees.py; the default build has none */
+/* why the last merge() of this thread had no result: 1 an input list was absent, 2 mergeVectors itself returned None */
+static _Thread_local int omo_merge_why;
+#define BC_MERGE(k) BC(omo_merge_why == 2 ? (k) : (k) + 1)          /* the counters of tests/test_search_trees.py */
 #else
 #define BC(k) ((void)0)
+#define BC_MERGE(k) ((void)0)
 #endif
 
 /* ---- a tiny arena of lists ------------------------------------------------------------------------------------- */
@@ -86,6 +90,9 @@ static OL *pass(OS *s, OL *l, int node, int up)
 }
 static OL *merge(OS *s, OL *l1, double b1, int t1, OL *l2, double b2, int t2, int upDown)
 {
+#ifdef OMO_BRANCH_COUNTS
+    omo_merge_why = (!l1 || !l2) ? 1 : 2;
+#endif
     if (!l1 || !l2) return NULL;
     OL *o = ol_new(s->a, l1->n + l2->n + 2);
     if (!o) return NULL;
@@ -197,6 +204,7 @@ int omo_findBestParentTopology(const OModel *m, const OTree *t, const OSearchPar
         PUSH(sibling, 0, 1, vectUpUp, d, bestLKdiff, 0, rpr1);
         bl[0] = t->dist[node]; bl[1] = t->dist[sibling]; bl[2] = removedBLen;
     } else {                                                          /* node is the root, M:6916-6960 */
+        BC(t->c0[sibling] >= 0 ? BC_SRCH_SEED_ROOT_SIB_INNER : BC_SRCH_SEED_ROOT_SIB_LEAF);
         if (t->c0[sibling] >= 0) {
             const int ch1 = t->c0[sibling], ch2 = t->c1[sibling];
             OL *v1 = pass(&S, tree_list(&S, 0, ch2), ch2, 1);
@@ -226,17 +234,27 @@ int omo_findBestParentTopology(const OModel *m, const OTree *t, const OSearchPar
                 OL *midTot;
                 if (upd) {
                     midTot = merge(&S, it.passed, distance / 2, 0, tree_list(&S, 0, t1), distance / 2, is_tip(t, t1), 1);
-                    if (!midTot) continue;
-                    if (!differ(&S, midTot, tree_list(&S, 3, t1))) upd = 0;
+                    if (!midTot) { BC_MERGE(BC_SRCH_DOWN_MID); continue; }
+                    if (!differ(&S, midTot, tree_list(&S, 3, t1))) { BC(BC_SRCH_DOWN_STOP); upd = 0; }
                 } else { midTot = tree_list(&S, 3, t1); distance = t->dist[t1]; }
                 if (!midTot) continue;
                 midProb = append(&S, midTot, it.rpr, isRemovedTip, removedBLen);
+                if (isinf(midProb)) BC(BC_SRCH_SCORE_MINUS_INF);
                 if (midProb > bestLKdiff - p->thrOptTopo) {
                     if (nR >= capR) return -3;
                     if (upd) { Rec r = {t1, midProb, it.passed, tree_list(&S, 0, t1), midTot, it.rpr, distance}; rec[nR++] = r; }
                     else { Rec r = {t1, midProb, NULL, NULL, NULL, it.rpr, 0.0}; rec[nR++] = r; }
                 }
-                if (midProb > bestLKdiff) { bestLKdiff = midProb; fails = 0; shorten_inplace(&S, it.rpr); }
+                if (midProb > bestLKdiff) {
+                    bestLKdiff = midProb; fails = 0;
+#ifdef OMO_BRANCH_COUNTS
+                    const int before = it.rpr->n;
+#endif
+                    shorten_inplace(&S, it.rpr);
+#ifdef OMO_BRANCH_COUNTS
+                    if (it.rpr->n != before) BC(it.rpr == rpr ? BC_SRCH_SHORTEN_OWN : BC_SRCH_SHORTEN_PASSED);
+#endif
+                }
                 else if (midProb < (it.lastLK - p->thrConsec)) fails++;
             } else midProb = it.lastLK;
             int go;
@@ -254,7 +272,7 @@ int omo_findBestParentTopology(const OModel *m, const OTree *t, const OSearchPar
                         OL *r1 = pass(&S, it.rpr, ch, 0);
                         if (upd) { vUp = pass(&S, vUp, ch, 0); PUSH(ch, 0, 1, vUp, t->dist[ch], midProb, fails, r1); }
                         else PUSH(ch, 0, 0, NULL, 0.0, midProb, fails, r1);
-                    }
+                    } else if (upd) BC_MERGE(BC_SRCH_DOWN_VUP);
                 }
             }
         } else {
@@ -266,17 +284,26 @@ int omo_findBestParentTopology(const OModel *m, const OTree *t, const OSearchPar
                 if (upd) {
                     OL *opv = pass(&S, tree_list(&S, 0, other), other, 1);
                     midBottom = merge(&S, it.passed, distance, 0, opv, t->dist[other], is_tip(t, other), 0);
-                    if (!midBottom) continue;
+                    if (!midBottom) { BC_MERGE(BC_SRCH_UP_BOTTOM); continue; }
                     vectUp = pass(&S, tree_list(&S, t->c0[upT] == t1 ? 1 : 2, upT), t1, 0);
                     midTot = merge(&S, vectUp, t->dist[t1] / 2, 0, midBottom, t->dist[t1] / 2, 0, 1);
                     OL *cached = tree_list(&S, 3, t1);
-                    if (!cached)                                      /* M:7198-7200 */
+#ifdef OMO_BRANCH_COUNTS
+                    const int whyMid = omo_merge_why;
+#endif
+                    if (!cached) {                                    /* M:7198-7200 */
+                        BC(BC_SRCH_UP_TOTUP_ON_THE_SPOT);
                         cached = merge(&S, vectUp, t->dist[t1] / 2, 0, tree_list(&S, 0, t1), t->dist[t1] / 2, 0, 1);
-                    if (!midTot) continue;
-                    if (!differ(&S, midTot, cached)) upd = 0;
+                    }
+#ifdef OMO_BRANCH_COUNTS
+                    omo_merge_why = whyMid;
+#endif
+                    if (!midTot) { BC_MERGE(BC_SRCH_UP_MID); continue; }
+                    if (!differ(&S, midTot, cached)) { BC(BC_SRCH_UP_STOP); upd = 0; }
                 } else midTot = tree_list(&S, 3, t1);
                 if (!midTot) continue;
                 midProb = append(&S, midTot, it.rpr, isRemovedTip, removedBLen);
+                if (isinf(midProb)) BC(BC_SRCH_SCORE_MINUS_INF);
                 if (midProb >= (bestLKdiff - p->thrOptTopo)) {
                     if (nR >= capR) return -3;
                     if (upd) { Rec r = {t1, midProb, vectUp, midBottom, midTot, it.rpr, t->dist[t1]}; rec[nR++] = r; }
@@ -296,19 +323,26 @@ int omo_findBestParentTopology(const OModel *m, const OTree *t, const OSearchPar
                     OL *vUpUp = pass(&S, tree_list(&S, upChild == 0 ? 1 : 2, upT), t1, 0);
                     vUp = merge(&S, vUpUp, t->dist[t1], 0, it.passed, distance, 0, 1);
                 } else vUp = tree_list(&S, it.dir == 1 ? 2 : 1, t1);
-                if (!vUp) continue;
+                if (!vUp) {
+#ifdef OMO_BRANCH_COUNTS
+                    if (!upd) omo_merge_why = 1;
+#endif
+                    BC_MERGE(BC_SRCH_UP_VUP);
+                    continue;
+                }
                 OL *r1 = pass(&S, it.rpr, other, 0);
                 if (upd) { vUp = pass(&S, vUp, other, 0); PUSH(other, 0, 1, vUp, t->dist[other], midProb, fails, r1); }
                 else PUSH(other, 0, 0, NULL, 0.0, midProb, fails, r1);
                 if (upd && !midBottom) {
                     OL *opv = pass(&S, tree_list(&S, 0, other), other, 1);
                     midBottom = merge(&S, it.passed, distance, 0, opv, t->dist[other], is_tip(t, other), 0);
-                    if (!midBottom) continue;
+                    if (!midBottom) { BC_MERGE(BC_SRCH_UP_BOTTOM_LATE); continue; }
                 }
                 r1 = pass(&S, it.rpr, t1, 1);
                 if (upd) { midBottom = pass(&S, midBottom, t1, 1); PUSH(upT, upChild + 1, 1, midBottom, t->dist[t1], midProb, fails, r1); }
                 else PUSH(upT, upChild + 1, 0, NULL, 0.0, midProb, fails, r1);
             } else {
+                BC(upd ? BC_SRCH_ROOT_CROSS_UPDATING : BC_SRCH_ROOT_CROSS_CACHED);
                 OL *r1 = pass(&S, it.rpr, other, 0);
                 if (upd) {
                     OL *vUp = root_vector(&S, it.passed, distance, 0, t1);
@@ -334,19 +368,19 @@ int omo_findBestParentTopology(const OModel *m, const OTree *t, const OSearchPar
             distance = t->dist[t1];
             midTot = tree_list(&S, 3, t1);
         } else { upV = r->up; downV = r->down; distance = r->distance; midTot = r->mid; }
-        if (!upV || !downV || !midTot) { res->nAppend = S.nAppend; return -1; }
+        if (!upV || !downV || !midTot) { BC(BC_SRCH_REFINE_NO_LIST); res->nAppend = S.nAppend; return -1; }
         const int ft = is_tip(t, t1);
         const size_t save = A.used;
         const double app = blen(&S, midTot, r->rpr, isRemovedTip);
         OL *midLower = merge(&S, downV, distance / 2, ft, r->rpr, app, isRemovedTip, 0);
-        if (!midLower) { res->nAppend = S.nAppend; return -1; }                                     /* the reference raises; its worker swallows it */
+        if (!midLower) { BC_MERGE(BC_SRCH_REFINE_LOWER); res->nAppend = S.nAppend; return -1; }   /* the reference raises; its worker swallows it */
         double top = blen(&S, upV, midLower, 0);
         OL *midTop = merge(&S, upV, top, 0, r->rpr, app, isRemovedTip, 1);
-        if (!midTop) { top = p->defaultBLen * 0.1; midTop = merge(&S, upV, top, 0, r->rpr, app, isRemovedTip, 1); }
-        if (!midTop) { res->nAppend = S.nAppend; return -1; }
+        if (!midTop) { BC(BC_SRCH_REFINE_TOP_RETRY); top = p->defaultBLen * 0.1; midTop = merge(&S, upV, top, 0, r->rpr, app, isRemovedTip, 1); }
+        if (!midTop) { BC(BC_SRCH_REFINE_TOP_NONE); res->nAppend = S.nAppend; return -1; }
         const double bottom = blen(&S, midTop, downV, ft);
         OL *newMid = merge(&S, upV, top, 0, downV, bottom, ft, 1);
-        if (!newMid) { res->nAppend = S.nAppend; return -1; }
+        if (!newMid) { BC(BC_SRCH_REFINE_NEWMID_NONE); res->nAppend = S.nAppend; return -1; }
         const double cost = append(&S, newMid, r->rpr, isRemovedTip, app);
         const double initialCost = append(&S, upV, downV, ft, distance);
         const double newPartialCost = append(&S, upV, downV, ft, bottom + top);
@@ -388,18 +422,22 @@ int omo_sprWorker(const OModel *m, const OTree *t, const OSearchParams *p, int n
         double cur;
         omo_appendProbNode(m, vectUp->e, vectUp->n, low->e, low->n, is_tip(t, node), t->dist[node], &cur);
         r->currentLK = cur;
-        if (!(cur < p->thrPlacement || t->dist[node] != 0.0)) { r->status = 2; continue; }
+        if (!(cur < p->thrPlacement || t->dist[node] != 0.0)) { BC(BC_SRCH_STATUS_2); r->status = 2; continue; }
         int rc = omo_findBestParentTopology(m, t, p, parent, child, cur, t->dist[node], r, arenaMem, arenaBytes);
-        if (rc != 0) { r->status = rc; continue; }                    /* (-1: nAppend = the calls issued before the reference raises) */
+        if (rc != 0) {                                               /* (-1: nAppend = the calls issued before the reference raises) */
+            if (rc == -1) BC(BC_SRCH_STATUS_MINUS_1);
+            r->status = rc;
+            continue;
+        }
         if (r->bestScore + p->thrPlacement > cur) {                   /* M:9681-9700 */
             int updated = 1;
             int topNode = t->up[node];
-            if (r->bestNode == topNode) updated = 0;
-            while (t->dist[topNode] == 0.0 && t->up[topNode] >= 0) topNode = t->up[topNode];
-            if (r->bestNode == topNode && r->blen[1] == 0.0) updated = 0;
+            if (r->bestNode == topNode) { BC(BC_SRCH_VETO_PARENT); updated = 0; }
+            while (t->dist[topNode] == 0.0 && t->up[topNode] >= 0) { BC(BC_SRCH_CHAIN_STEP); topNode = t->up[topNode]; }
+            if (r->bestNode == topNode && r->blen[1] == 0.0) { BC(BC_SRCH_VETO_CHAIN_TOP); updated = 0; }
             const int sib = t->c0[parent] == node ? t->c1[parent] : t->c0[parent];
-            if (r->bestNode == sib) updated = 0;
-            if (t->up[r->bestNode] == sib && r->blen[0] == 0.0) updated = 0;
+            if (r->bestNode == sib) { BC(BC_SRCH_VETO_SIBLING); updated = 0; }
+            if (t->up[r->bestNode] == sib && r->blen[0] == 0.0) { BC(BC_SRCH_VETO_BELOW_SIBLING); updated = 0; }
             if (updated) { r->improvement = r->bestScore - cur; r->placement = r->bestNode; }
         }
     }

@@ -34,14 +34,20 @@ def build_counting_oracle(out_dir):
     return out
 
 
-def read_counts(lib, reset=True):
+def read_counts(lib, reset=True, fn="omo_branch_counts"):
     """{counter: hits} of a counting build of the oracle since the last reset"""
     import ctypes as C
-    n = lib.omo_branch_counts(None, None, 0, 0)
+    get = getattr(lib, fn)
+    n = get(None, None, 0, 0)
     vals = (C.c_longlong * n)()
     names = (C.c_char_p * n)()
-    lib.omo_branch_counts(vals, names, n, int(reset))
+    get(vals, names, n, int(reset))
     return {names[k].decode(): int(vals[k]) for k in range(n)}
+
+
+def read_search_counts(lib, reset=True):
+    """the same for the counters of the SPR search's arms (OMO_BC_SEARCH_LIST), which the operators' list leaves out"""
+    return read_counts(lib, reset, "omo_search_branch_counts")
 
 
 def tup(gl):
