@@ -89,6 +89,23 @@ int maple_debug_frontier_pass_batch(maple_ctx *ctx, int32_t n, const int32_t *li
 int maple_debug_score_rows(maple_ctx *ctx, int32_t form, int32_t nQ, const int32_t *qList, const uint8_t *qTip, const double *qBLen,
                            int32_t nC, const int32_t *cand, const int32_t *outCol /* or NULL */, int64_t ldOut, double fill, double *out,
                            uint64_t *finMask, int32_t *prefix, int64_t *pairsWalked /* or NULL */);
+/* One level's items of maple_update_partials / maple_tree_rebuild_lists on explicit lists, by the library's own host function and
+ * fused kernels (maple_amd/csrc/update.hip: one wavefront per item up to the tuning's wavePerItemMax, one lane per item above it).
+ * Item i: mergeVectors(l1, b1, t1, l2, b2, t2, upDown), then by mode[i] -- 0: shorten(), then areVectorsDifferent(new, old);
+ * 1: shorten(); 2: areVectorsDifferent(old, new) and shorten() only if they differ.  old[i] = -1: nothing to compare with.
+ * outList[i]: the new list (-1: the merge is None, or mode 2 and not different); outNone[i] = 1 if the merge is None; outDiff[i]:
+ * the verdict (1 where none was asked). */
+int maple_debug_update_items(maple_ctx *ctx, int32_t n, const int32_t *l1, const double *b1, const uint8_t *t1, const int32_t *l2,
+                             const double *b2, const uint8_t *t2, const uint8_t *upDown, const uint8_t *mode, const int32_t *old,
+                             int32_t *outList, uint8_t *outNone, uint8_t *outDiff);
+/* The arms the last maple_update_partials of this context took (maple_amd/csrc/update_plan.h, UPDATE_PLAN_STATS): *n counters, the
+ * first min(*n, cap) written; maple_debug_update_partials_stat_names gives their names in the same order, each followed by a blank. */
+int maple_debug_update_partials_stats(maple_ctx *ctx, int64_t *counts, int32_t cap, int32_t *n);
+const char *maple_debug_update_partials_stat_names(void);
+/* The nodes that call visited, with repeats, in the order of the visits: the changed nodes, every node that entered a level of the
+ * repair, the nodes whose length was estimated again and their parents -- the ones the reference's updatePartials sets `dirty` for,
+ * and what maple_tree_optimize_blens takes them from.  *n nodes; more than cap is an error. */
+int maple_debug_update_partials_visited(maple_ctx *ctx, int32_t cap, int32_t *nodes, int32_t *n);
 
 #ifdef __cplusplus
 }

@@ -153,6 +153,15 @@ const std::vector<int32_t> &update_partials_visited(maple_ctx *c);
 // the list behind maple_update_partials_touched (a caller that repairs in several calls stores the union here)
 __attribute__((visibility("hidden")))
 std::vector<int32_t> &update_partials_replaced(maple_ctx *c);
+// the counters of the last maple_update_partials (update_plan::Stats, in the order of UPDATE_PLAN_STATS): writes the first
+// min(cap, their number) and returns their number
+__attribute__((visibility("hidden")))
+int update_partials_stats(maple_ctx *c, int32_t cap, int64_t *counts);
+// one level's items of the repair (the fused kernels k_update_items / k_update_items_wave): see update.hip
+__attribute__((visibility("hidden")))
+int update_items(maple_ctx *c, int32_t n, const int32_t *l1, const double *b1, const uint8_t *t1, const int32_t *l2, const double *b2,
+                 const uint8_t *t2, const uint8_t *ud, const uint8_t *mode, const int32_t *old, int32_t *outList, uint8_t *outNone,
+                 uint8_t *outDiff);
 // ---- defined in spr_batch.hip ----------------------------------------------------------------------------------------------
 // the device tree once more from the host copy of its columns (after maple_tree_patch left tables stale)
 __attribute__((visibility("hidden")))

@@ -7,6 +7,7 @@
 #include "frontier.h"
 #include "frontier_dev.h"
 #include "witness.h"
+#include "update_plan.h"
 
 #include <algorithm>
 
@@ -418,4 +419,43 @@ extern "C" int maple_debug_score_rows(maple_ctx *c, int32_t form, int32_t nQ, co
     HIPCK(c, hipStreamSynchronize(c->stream));
     if (pairsWalked) *pairsWalked = pairs;
     return MAPLE_OK;
+}
+
+// ---- the repair's fused item kernels on explicit lists, and the arms the last repair took -------------------------------------
+// update_items of update.hip itself (staging, the choice of kernel by wave_item_max, commit_known): nothing of it is repeated here.
+extern "C" int maple_debug_update_items(maple_ctx *c, int32_t n, const int32_t *l1, const double *b1, const uint8_t *t1, const int32_t *l2,
+                                        const double *b2, const uint8_t *t2, const uint8_t *upDown, const uint8_t *mode, const int32_t *old,
+                                        int32_t *outList, uint8_t *outNone, uint8_t *outDiff)
+{
+    if (!c || n < 0 || !l1 || !b1 || !t1 || !l2 || !b2 || !t2 || !upDown || !mode || !old || !outList || !outNone || !outDiff) return MAPLE_ERR_ARG;
+    for (int i = 0; i < n; i++)
+        if (mode[i] > 2) return fail(c, MAPLE_ERR_ARG, "mode[%d] = %d", i, mode[i]);
+    TRY(need_model(c));
+    return update_items(c, n, l1, b1, t1, l2, b2, t2, upDown, mode, old, outList, outNone, outDiff);
+}
+
+extern "C" int maple_debug_update_partials_stats(maple_ctx *c, int64_t *counts, int32_t cap, int32_t *n)
+{
+    if (!c || cap < 0 || !n || (cap && !counts)) return MAPLE_ERR_ARG;
+    *n = update_partials_stats(c, cap, counts);
+    return MAPLE_OK;
+}
+
+// the nodes the last maple_update_partials visited, with repeats and in the order of the visits (update_partials_visited of update.hip:
+// what the branch-length sweep sets `dirty` from)
+extern "C" int maple_debug_update_partials_visited(maple_ctx *c, int32_t cap, int32_t *nodes, int32_t *n)
+{
+    if (!c || cap < 0 || !n || (cap && !nodes)) return MAPLE_ERR_ARG;
+    const std::vector<int32_t> &vis = update_partials_visited(c);
+    *n = (int32_t)vis.size();
+    if ((int32_t)vis.size() > cap) return fail(c, MAPLE_ERR_ARG, "%zu visited nodes do not fit in %d", vis.size(), cap);
+    for (size_t i = 0; i < vis.size(); i++) nodes[i] = vis[i];
+    return MAPLE_OK;
+}
+
+extern "C" const char *maple_debug_update_partials_stat_names(void)
+{
+#define UPDATE_PLAN_STAT_NAME(name) #name " "
+    return UPDATE_PLAN_STATS(UPDATE_PLAN_STAT_NAME);
+#undef UPDATE_PLAN_STAT_NAME
 }

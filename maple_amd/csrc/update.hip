@@ -119,7 +119,8 @@ static UpdateScratch &update_scratch(maple_ctx *c)
 // One level's worth of items through k_update_items: merge, then shorten / compare as the item's mode says (see the
 // kernel).  outList[i]: the new list (-1: None from the merge, or mode 2 and not different: nothing to replace);
 // outNone[i] = 1 if the merge itself came out None; outDiff[i] = the areVectorsDifferent verdict (1 where none was asked).
-static int update_items(maple_ctx *c, int32_t n, const int32_t *l1, const double *b1, const uint8_t *t1, const int32_t *l2,
+// (batch_host.h: maple_debug_update_items of the debug library runs it on the caller's own lists)
+int update_items(maple_ctx *c, int32_t n, const int32_t *l1, const double *b1, const uint8_t *t1, const int32_t *l2,
                         const double *b2, const uint8_t *t2, const uint8_t *ud, const uint8_t *mode, const int32_t *old,
                         int32_t *outList, uint8_t *outNone, uint8_t *outDiff)
 {
@@ -221,6 +222,19 @@ extern "C" int maple_update_partials(maple_ctx *c, int32_t n, int32_t root, cons
 // visited, and the list maple_update_partials_touched reports, which the sweep replaces by the union over its repairs
 const std::vector<int32_t> &update_partials_visited(maple_ctx *c) { return update_scratch(c).visitedNodes; }
 std::vector<int32_t> &update_partials_replaced(maple_ctx *c) { return update_scratch(c).replacedNodes; }
+// the counters of update_plan::Stats of the last maple_update_partials, in the order of UPDATE_PLAN_STATS: the first cap of them
+int update_partials_stats(maple_ctx *c, int32_t cap, int64_t *counts)
+{
+    const update_plan::Stats &st = update_scratch(c).stats;
+    const int64_t all[] = {
+#define UPDATE_PLAN_STAT_VALUE(name) st.name,
+        UPDATE_PLAN_STATS(UPDATE_PLAN_STAT_VALUE)
+#undef UPDATE_PLAN_STAT_VALUE
+    };
+    const int32_t n = (int32_t)(sizeof all / sizeof all[0]);
+    for (int32_t k = 0; k < n && k < cap; k++) counts[k] = all[k];
+    return n;
+}
 
 // the nodes whose lists (or branch length) the last maple_update_partials replaced, each once, ascending: what a caller
 // has to tell maple_tree_patch about besides its own tree edit

@@ -143,6 +143,23 @@ struct Batch {
     }
 };
 
+// Which arms the last repair took, for the tests (maple_debug_update_partials_stats): the names once, in the order of the counters.
+// rounds: rounds of phase A + phase B; phaseA_none: a lower merge that came out None between two zero-length branches, and the
+// branch re-estimated first / second for it; upper_none_*: a None upper merge by kind, the ones skipped because the node's other
+// merge had dealt with it, and the re-estimates of the node's / the merged child's branch; root_*: the root's upper lists made
+// (probVectUpRight / UpLeft) or kept because rootVector came out as it was; totup_cleared: a probVectTotUp dropped over length 0;
+// items_*: the items of the level batches by mode, and those of mode 0 / 2 that had no old list to compare with.
+#define UPDATE_PLAN_STATS(X)                                                                                                     \
+    X(rounds) X(phaseA_none) X(phaseA_reest_first) X(phaseA_reest_second)                                                        \
+    X(upper_none_totup) X(upper_none_upright) X(upper_none_upleft) X(upper_deferred_skip) X(upper_reest_node) X(upper_reest_child) \
+    X(root_right_made) X(root_left_made) X(root_kept) X(totup_cleared)                                                           \
+    X(items_mode0) X(items_mode1) X(items_mode2) X(items_old_absent)
+struct Stats {
+#define UPDATE_PLAN_STAT_FIELD(name) int64_t name = 0;
+    UPDATE_PLAN_STATS(UPDATE_PLAN_STAT_FIELD)
+#undef UPDATE_PLAN_STAT_FIELD
+};
+
 struct Scratch {                                  // persistent between calls: flags per node, cleared through the touched list
     std::vector<uint8_t> dLow, dUp, dDist, dCh0, dCh1, inFrontier, inTodo;
     std::vector<int32_t> touched;
@@ -151,6 +168,7 @@ struct Scratch {                                  // persistent between calls: f
     std::vector<int32_t> visitedNodes;    // nodes the last call visited (with repeats): the changed nodes, every node that entered
                                           // phase A's frontier or phase B's todo list, the nodes whose length was re-estimated --
                                           // the ones the reference's updatePartials sets `dirty` for (M:5499-5500, 5410-5411)
+    Stats stats;                          // the arms the last call took
     void fit(size_t n)
     {
         if (dLow.size() < n) {
@@ -191,6 +209,15 @@ template <class Ops> struct Repair {
         if (!okNode(p)) return;
         markChild(p, T.c0[p] == v ? 0 : 1);
         if (!S.inFrontier[p]) { S.inFrontier[p] = 1; frontier.push_back(p); }
+    }
+    // the level's batch, counted by mode, then run
+    int runBatch()
+    {
+        for (size_t k = 0; k < B.size(); k++) {
+            (B.mode[k] == 0 ? S.stats.items_mode0 : B.mode[k] == 1 ? S.stats.items_mode1 : S.stats.items_mode2)++;
+            if (B.mode[k] != 1 && B.old[k] < 0) S.stats.items_old_absent++;
+        }
+        return B.run(T, ops);
     }
     void addTodo(int v) { if (!S.inTodo[v]) { S.inTodo[v] = 1; S.touch(v); todo.push_back(v); } }
     // the nodes of `work` at its deepest / shallowest depth, ascending, into `nodes`; the others stay
@@ -242,9 +269,10 @@ template <class Ops> struct Repair {
             for (int v : nodes)
                 if (!F.lower(T, v, 0)) return E.fail(ERR_ARG, "node %d has a changed child but no two (valid) children", v);
             B.done(F);
-            UP_TRY(B.run(T, ops));
+            UP_TRY(runBatch());
             for (size_t k = 0; k < B.size(); k++) {
                 if (!B.none[k]) continue;
+                S.stats.phaseA_none++;
                 // None between two zero-length branches: re-estimate the branch above the changed child, like updateBLen
                 // (M:5385-5414, 5689-5701)
                 const int p = nodes[k];
@@ -255,6 +283,7 @@ template <class Ops> struct Repair {
                     const int which = oi == 0 ? first : 1 - first;
                     const int ch = which == 0 ? T.c0[p] : T.c1[p];
                     UP_TRY(reestimate(ch));
+                    (oi == 0 ? S.stats.phaseA_reest_first : S.stats.phaseA_reest_second)++;
                     S.dLow[ch] = 1; S.dDist[ch] = 1; S.touch(ch);
                     markChild(p, which);
                     if (T.dist[ch] != 0.0) break;
@@ -262,6 +291,9 @@ template <class Ops> struct Repair {
                 B.b1[k] = T.dist[B.kid1[k]]; B.b2[k] = T.dist[B.kid2[k]];
                 UP_TRY(ops.items(B, k, (size_t)1));
                 if (B.none[k]) return E.fail(ERR_FATAL, "None vector after updateBLen at node %d", p);
+                // (after updateBLen the reference goes on to p's parent whatever the new list looks like -- madeChange, M:5694,
+                // 5808-5812 -- and sets `dirty` for it; here the new list decides below, and the parent counts as visited)
+                if (okNode(T.up[p])) S.visitedNodes.push_back(T.up[p]);
             }
             for (size_t k = 0; k < B.size(); k++) {
                 const int v = nodes[k];
@@ -291,7 +323,8 @@ template <class Ops> struct Repair {
             const int32_t have = which == 1 ? T.upRight[r] : T.upLeft[r];
             uint8_t df = 1;
             if (have >= 0) UP_TRY(ops.differ(have, res, &df));
-            if (df) newUpper(r, which == 1 ? UP_RIGHT : UP_LEFT, res);
+            if (df) { newUpper(r, which == 1 ? UP_RIGHT : UP_LEFT, res); (which == 1 ? S.stats.root_right_made : S.stats.root_left_made)++; }
+            else S.stats.root_kept++;
         }
         return 0;
     }
@@ -306,7 +339,8 @@ template <class Ops> struct Repair {
             fprintf(stderr, "[maple] updatePartials round %d: None %s at node %d (length %.3g), child %d (length %.3g), merged with b1 %.3g b2 %.3g\n",
                     roundNo, B.kind[i] == TOT_UP ? "probVectTotUp" : (B.kind[i] == UP_RIGHT ? "probVectUpRight" : "probVectUpLeft"), v, T.dist[v], kd,
                     kd >= 0 ? T.dist[kd] : -1.0, B.b1[i], B.b2[i]);
-        if (std::find(deferred.begin(), deferred.end(), v) != deferred.end()) return 0;   // (its other merge already dealt with it)
+        (B.kind[i] == TOT_UP ? S.stats.upper_none_totup : B.kind[i] == UP_RIGHT ? S.stats.upper_none_upright : S.stats.upper_none_upleft)++;
+        if (std::find(deferred.begin(), deferred.end(), v) != deferred.end()) { S.stats.upper_deferred_skip++; return 0; }   // (its other merge already dealt with it)
         if (B.kind[i] != TOT_UP && (T.dist[v] != 0.0 || T.dist[kd] != 0.0))
             return E.fail(ERR_FATAL, "None upper vector from non-zero distances at node %d (the reference raises too)", v);
         deferred.push_back(v);
@@ -314,6 +348,7 @@ template <class Ops> struct Repair {
         for (int w : {v, kd}) {
             if (w < 0 || T.up[w] < 0) continue;
             UP_TRY(reestimate(w));
+            (w == v ? S.stats.upper_reest_node : S.stats.upper_reest_child)++;
             S.visitedNodes.push_back(w);
             S.visitedNodes.push_back(T.up[w]);
             if (T.dist[w] != 0.0) { next.push_back(w); return 0; }
@@ -348,7 +383,7 @@ template <class Ops> struct Repair {
             for (size_t k = 0; k < nodes.size(); k++) {
                 const int v = nodes[k];
                 if (S.dUp[v] || S.dLow[v]) {
-                    if (T.dist[v] == 0.0) { if (T.totUp[v] != -1) S.replacedNodes.push_back(v); T.totUp[v] = -1; }
+                    if (T.dist[v] == 0.0) { if (T.totUp[v] != -1) S.replacedNodes.push_back(v); T.totUp[v] = -1; S.stats.totup_cleared++; }
                     else F.totUp(T, v, vu[k]);
                 }
                 if (T.c0[v] < 0) continue;
@@ -358,7 +393,7 @@ template <class Ops> struct Repair {
             }
             B.done(F);
             if (B.size() == 0) continue;
-            UP_TRY(B.run(T, ops));
+            UP_TRY(runBatch());
             deferred.clear();                                              // nodes of this level that met an inconsistency
             for (size_t i = 0; i < B.size(); i++) if (B.none[i]) UP_TRY(noneUpper(i));
             // (the reference recomputes ALL of such a node's vectors with the new length before anything goes on to its children,
@@ -391,6 +426,7 @@ int repair_drive(const Tree &T, Scratch &S, Ops &ops, int32_t nChanged, const in
     S.clear();
     S.replacedNodes.clear();
     S.visitedNodes.clear();
+    S.stats = Stats{};
     Repair<Ops> R{T, S, ops, E, verbose};
     std::vector<int32_t> chg(changed, changed + nChanged);
     int rc = 0;
@@ -398,6 +434,7 @@ int repair_drive(const Tree &T, Scratch &S, Ops &ops, int32_t nChanged, const in
         if (round >= 64) { rc = E.fail(ERR_FATAL, "updatePartials keeps finding inconsistent zero-length branches"); break; }
         R.next.clear();
         R.roundNo = round;
+        S.stats.rounds++;
         R.redoNow.swap(R.redoNext);
         R.redoNext.clear();
         rc = R.round(chg);

@@ -583,6 +583,37 @@ class Device:
                                                  ld, fill, _ptr(out), _ptr(mask), _ptr(prefix), C.byref(pairs)))
         return out, mask, prefix, pairs.value
 
+    def debug_update_items(self, l1, b1, tip1, l2, b2, tip2, upDown, mode, old):
+        """One level's items of the repair by the library's own fused kernels (maple_debug_update_items): mergeVectors, then
+        shorten / areVectorsDifferent as mode 0 / 1 / 2 says, against old (-1: none).  Returns (list ids, -1 where the merge is None
+        or mode 2 found no difference; None flags; verdicts)."""
+        l1, l2, old = _i32(l1), _i32(l2), _i32(old)
+        n = len(l1)
+        b1, b2 = _f64(np.broadcast_to(b1, n)), _f64(np.broadcast_to(b2, n))
+        t1, t2, ud, md = (_u8(np.broadcast_to(x, n)) for x in (tip1, tip2, upDown, mode))
+        out = np.full(n, -1, dtype=np.int32)
+        none, diff = np.zeros(n, dtype=np.uint8), np.zeros(n, dtype=np.uint8)
+        self._ck(self.lib.maple_debug_update_items(self.h, n, _ptr(l1), _ptr(b1), _ptr(t1), _ptr(l2), _ptr(b2), _ptr(t2), _ptr(ud), _ptr(md),
+                                                   _ptr(old), _ptr(out), _ptr(none), _ptr(diff)))
+        return out, none.astype(bool), diff.astype(bool)
+
+    def debug_update_partials_stats(self):
+        """The arms the last update_partials took (maple_debug_update_partials_stats): {counter name: count}, the names as the
+        library gives them (update_plan.h, UPDATE_PLAN_STATS)."""
+        names = self.lib.maple_debug_update_partials_stat_names().decode().split()
+        counts = np.zeros(len(names), dtype=np.int64)
+        n = C.c_int32()
+        self._ck(self.lib.maple_debug_update_partials_stats(self.h, _ptr(counts), len(counts), C.byref(n)))
+        assert n.value == len(names), (n.value, names)
+        return dict(zip(names, (int(x) for x in counts)))
+
+    def debug_update_partials_visited(self, cap=65536):
+        """The nodes the last update_partials visited, with repeats, in order (maple_debug_update_partials_visited)."""
+        nodes = np.zeros(cap, dtype=np.int32)
+        n = C.c_int32()
+        self._ck(self.lib.maple_debug_update_partials_visited(self.h, cap, _ptr(nodes), C.byref(n)))
+        return nodes[: n.value].copy()
+
     def debug_calib_walk(self, nbytes, repeats=1):
         ms = C.c_float()
         self._ck(self.lib.maple_debug_calib_walk(self.h, nbytes, repeats, C.byref(ms)))

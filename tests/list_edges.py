@@ -1234,3 +1234,207 @@ def oracle_rows(o, queries, cands, qTip, qBLen):
     want = np.full((nQ, nC), -np.inf)
     want[:, have] = o.appendProbNode_batch(packed, pi, len(have) + qi, tip, bl).reshape(nQ, len(have))
     return want
+
+
+# ---- the fused items of the list repair (k_update_items / k_update_items_wave of maple_amd/csrc/update.hip) -------------------------
+# An item is (l1, b1, t1, l2, b2, t2, upDown, mode, old): mergeVectors, then by mode 0: shorten, areVectorsDifferent(new, old);
+# 1: shorten; 2: areVectorsDifferent(old, unshortened new), shorten only if different.  Every item of the family runs in all three modes.
+UPDATE_SIZES = (1, 63, 64, 65, 256, 257)                          # entries of an input list: around a chunk of lanes and the staging limit
+UPDATE_MERGED = (64, 65, 128)                                     # entries of a merged list (and one of at least 449)
+ALL_N = [(5, L_REF)]
+
+
+def sized(ref, u, rng, n, first):
+    """a list of exactly n entries: n - 1 adjacent single-site entries from position `first` on, then R to the end (n = 1: all R)"""
+    b = Builder(ref, u)
+    if first > 1 and n > 1:
+        b.run(4, 1, first - 1)
+        n -= 1
+    for p in range(first, first + n - 1):
+        b.nuc(p, other(rng, int(ref[p - 1])))
+    out = b.done()
+    return out
+
+
+def tied_runs(ref, u, n_runs, width, second):
+    """n_runs entries that all end at multiples of `width`: two such lists end every merge step at the same position (the tie rule
+    of merge_path at every step, also at steps 63 / 64 and 127 / 128).  second: the other list, N and R runs in turn."""
+    b = Builder(ref, u)
+    for k in range(n_runs):
+        s, e = k * width + 1, (k + 1) * width
+        if second:
+            b.run(5 if k % 3 == 1 else 4, s, e, d0=(2e-4 if k % 3 == 2 else None), flag=False)
+        else:
+            b.run(4, s, e, d0=1e-4 * (1 + k % 5), flag=bool(k % 2))
+    return b.done()
+
+
+def perturbed_copies(rng, new, u, limit=None):
+    """[(name, threshold case?, copy of `new` changed in one place)] the way fam_differ_edges and the stop-rule test perturb: the
+    type, the tuple length, d0, d1 and the flag of an entry, O components as in WINDOW.  limit: at most this many, taken evenly."""
+    out = []
+    seen = {}
+    for k, e in enumerate(new):
+        kind = (e[0] if e[0] >= 4 else 0, len(e))
+        if seen.setdefault(kind, 0) >= 1:
+            continue
+        seen[kind] += 1
+        t = e[0]
+        if t == 6:
+            vec = e[-1]
+            i = int(np.argmin(vec))
+            for (x, y, _) in WINDOW:
+                moved = vec[i] * (y / x) if x > 0.0 else 0.0
+                if moved == vec[i] or moved >= 1.0 or vec[i] >= 1.0:
+                    continue
+                scale = (1.0 - moved) / (1.0 - vec[i])
+                out.append((("O", x, y), True, replace_entry(new, k, e[:-1] + ([moved if j == i else vec[j] * scale for j in range(4)],))))
+            if len(e) == 4:
+                out.append(("O_d0_far", False, replace_entry(new, k, (6, e[1], e[2] + 2 * THR, e[3]))))
+                out.append(("O_d0_near", True, replace_entry(new, k, (6, e[1], e[2] + 0.5 * THR, e[3]))))
+                out.append(("O_len", False, replace_entry(new, k, (6, e[1], e[3]))))
+            out.append(("O_to_nuc", False, replace_entry(new, k, ((e[1] + 1) % 4, e[1]))))
+        elif t == 5:
+            out.append(("N_to_R", False, replace_entry(new, k, (4, e[1]))))
+        elif len(e) == 2:
+            out.append(("bare_to_tail", False, replace_entry(new, k, (t, e[1], 1e-4) + ((False,) if u else ()))))
+            if t < 4:
+                out.append(("nuc_type", False, replace_entry(new, k, (next(z for z in range(4) if z not in (t, e[1])), e[1]))))
+        else:
+            out.append(("d0_far", False, replace_entry(new, k, e[:2] + (e[2] + 2 * THR,) + e[3:])))
+            out.append(("d0_near", True, replace_entry(new, k, e[:2] + (e[2] + 0.5 * THR,) + e[3:])))
+            if len(e) == 4 + u:
+                out.append(("d1_far", False, replace_entry(new, k, e[:3] + (e[3] + 2 * THR,) + e[4:])))
+                out.append(("d1_near", True, replace_entry(new, k, e[:3] + (e[3] + 0.5 * THR,) + e[4:])))
+                out.append(("len", False, replace_entry(new, k, e[:3] + e[4:])))
+            if u:
+                out.append(("flag", False, replace_entry(new, k, e[:-1] + (not e[-1],))))
+    if limit is not None and len(out) > limit:
+        out = [out[int(j)] for j in np.linspace(0, len(out) - 1, limit).round()]
+    return out
+
+
+def fam_update_items(mode, o):
+    """(lists, items) of a mode for the oracle o (set to that mode).  items: dicts with i1, i2, iold (indices into lists; iold -1: no
+    old list), b1, t1, b2, t2, ud, name = (pair name, form of old), threshold (the verdict hangs on a value within the thresholds
+    of areVectorsDifferent), and the oracle's m (the merge, None if there is none) and s (shorten(m)).  Pairs come from the merge
+    families and the skipping-form edges, from the shorten families merged with an all-N list (so that shorten after the merge has
+    runs to absorb and to refuse: the run-head rule, the flag), and from lists built for the shapes the fused kernels cut their
+    work along (the names starting with "shape")."""
+    ref = reference()
+    u = bool(model(mode).get("usingErrorRate"))
+    rng = np.random.default_rng(500 + MODES.index(mode))
+    corp = corpus(mode)
+    pairs = []                                                     # (name, pv1, b1, t1, pv2, b2, t2, ud)
+    for fam in ("merge_updown", "merge_carry"):
+        for k, c in enumerate(corp[fam]):
+            pairs.append(((fam, k), c["pv1"], c["b1"], c["tip1"], c["pv2"], c["b2"], c["tip2"], c["isUpDown"]))
+    longs = long_lists(rng, ref, u)
+    for k in range(0, len(longs) - 1, 2):
+        pairs.append((("long", k), longs[k], 1e-4, False, longs[k + 1], 2e-4, bool(k % 4 == 0), bool(k % 4 == 2)))
+    edges = skip_edge_lists(rng, ref, u)
+    names = sorted(edges)
+    for i, a in enumerate(names):
+        b = names[(i + 5) % len(names)]
+        pairs.append((("skip", a, b), edges[a], 1e-4, False, edges[b], 3e-4, bool(i % 2), bool(i % 3 == 0)))
+    for k in range(10):
+        up_down = bool(k % 2)
+        pairs.append((("rich", k), rich_list(rng, ref, u, [8, 20][k % 2], d1=up_down), 1e-4, False, rich_list(rng, ref, u, 15, d1=False), 2e-4,
+                      False, up_down))
+    for c in fam_shorten_runs(rng, ref, u):                        # shorten after the merge absorbs, or refuses on the head or the flag
+        lower_form_ok = all(not (e[0] <= 4 and len(e) == 4 + u) for e in c["vec"])
+        if len(c["vec"]) > 256:
+            continue
+        pairs.append((("shorten", c["name"]), c["vec"], 1e-4, False, ALL_N, 1e-4, False, not lower_form_ok))
+    # -- the shapes
+    for n1 in UPDATE_SIZES:
+        for n2 in UPDATE_SIZES:
+            pairs.append((("shape_sizes", n1, n2), sized(ref, u, rng, n1, 1), 1e-4, bool(n1 % 2), sized(ref, u, rng, n2, 700), 2e-4, bool(n2 % 2), False))
+    for want in UPDATE_MERGED + (449,):                            # a merged list of exactly `want` entries (>= for the last)
+        n1 = want // 2
+        a, b = sized(ref, u, rng, n1, 1), sized(ref, u, rng, want - n1 + 1, 700)   # (n1 - 1 sites, R, n2 - 2 sites, R)
+        pairs.append((("shape_merged", want), a, 1e-4, False, b, 1e-4, False, False))
+    for n_old in (512, 513):                                       # the old list at the staging limit and past it (inputs of 256 / 257)
+        a, b = sized(ref, u, rng, 256, 1), sized(ref, u, rng, n_old - 255, 700)
+        pairs.append((("shape_old", n_old), a, 1e-4, False, b, 1e-4, False, False))
+    pairs.append((("shape_ties", 140), tied_runs(ref, u, 140, 10, False), 1e-4, False, tied_runs(ref, u, 140, 10, True), 2e-4, False, False))
+    pairs.append((("shape_ties_updown", 140), tied_runs(ref, u, 140, 10, False), 1e-4, False, tied_runs(ref, u, 140, 10, True), 2e-4, False, True))
+    b = Builder(ref, u)                                            # one run absorbed across three chunks of 64 entries
+    for k in range(150):
+        b.run(4, 2 * k + 1, 2 * k + 2, d0=2e-4, flag=False)
+    pairs.append((("shape_absorb_three_chunks",), b.done(), 1e-4, False, ALL_N, 1e-4, False, False))
+    for lead in (61, 62, 63):                                      # O entries whose aux doubles straddle entry 64
+        b = prefix_sites(Builder(ref, u), rng, lead)
+        for p in range(lead + 1, lead + 5):
+            b.o(p, rng.dirichlet([1.0] * 4), d0=(1e-4 if p % 2 else None))
+        pairs.append((("shape_O_straddle", lead), b.done(), 1e-4, False, ALL_N, 1e-4, False, False))
+    # two lists that show different nucleotides at no distance: no merge (-1), at the first, a middle and the last step of the
+    # walk, and at two steps of one chunk of lanes
+    for name, ps in (("first", (1,)), ("middle", (700,)), ("last", (L_REF,)), ("two_in_a_chunk", (10, 20))):
+        a, b = Builder(ref, u), Builder(ref, u)
+        for p in ps:
+            r = int(ref[p - 1])
+            x = other(rng, r)
+            a.nuc(p, x)
+            b.nuc(p, other(rng, r, (x,)))
+        pairs.append((("shape_none", name), a.done(), 0.0, False, b.done(), 0.0, False, False))
+    lists, items = [], []
+
+    def put(gl):
+        lists.append([tuple(e) for e in gl])
+        return len(lists) - 1
+
+    for (name, pv1, b1, t1, pv2, b2, t2, ud) in pairs:
+        try:
+            m = o.mergeVectors(pv1, b1, t1, pv2, b2, t2, isUpDown=ud)
+        except RuntimeError:
+            continue                                               # (a state the reference raises on: not this family's)
+        i1, i2 = put(pv1), put(pv2)
+        s = None if m is None else o.shorten(m)
+        olds = [("absent", False, None)]
+        if m is not None:
+            few = 3 if name[0] in ("shape_sizes", "skip", "shorten") else 8
+            olds.append(("own", False, s))
+            olds += [(("moved",) + (nm if isinstance(nm, tuple) else (nm,)), thr, gl) for nm, thr, gl in perturbed_copies(rng, s, u, few)]
+            if m != s:
+                olds.append(("own_unshortened", False, m))
+                olds += [(("moved_unshortened",) + (nm if isinstance(nm, tuple) else (nm,)), thr, gl)
+                         for nm, thr, gl in perturbed_copies(rng, m, u, 3)]
+        for form, thr, old in olds:
+            items.append(dict(i1=i1, b1=float(b1), t1=bool(t1), i2=i2, b2=float(b2), t2=bool(t2), ud=bool(ud), iold=-1 if old is None else put(old),
+                              name=(name, form), threshold=thr, m=m, s=s))
+    return lists, items
+
+
+def update_item_expect(o, it, old, mode):
+    """(list or None, outNone, verdict) of an item in a mode, from the oracle alone"""
+    m, s = it["m"], it["s"]
+    if m is None:
+        return None, True, True
+    if mode == 0:
+        return s, False, (True if old is None else o.areVectorsDifferent(s, old))
+    if mode == 1:
+        return s, False, True
+    flag = True if old is None else o.areVectorsDifferent(old, m)
+    return (s if flag else None), False, flag
+
+
+def scaled(gl, f):
+    """the list with every double multiplied by f"""
+    def mul(x):
+        if isinstance(x, list):
+            return [z * f for z in x]
+        return x * f if isinstance(x, float) else x
+    return [e[:2] + tuple(mul(x) for x in e[2:]) for e in gl]
+
+
+def verdict_stable(o, it, old, mode, rel=1e-9):
+    """the oracle's verdict of a compared item is the same when every double of the new list moves by +-rel"""
+    new = it["s"] if mode == 0 else it["m"]
+    want = o.areVectorsDifferent(new, old) if mode == 0 else o.areVectorsDifferent(old, new)
+    for f in (1.0 + rel, 1.0 - rel):
+        moved = scaled(new, f)
+        got = o.areVectorsDifferent(moved, old) if mode == 0 else o.areVectorsDifferent(old, moved)
+        if got != want:
+            return False
+    return True

@@ -183,8 +183,13 @@ def parse_log(line):
 
 def parse_book(line):
     assert line.startswith("B"), line
-    rep, vis, zero = line[1:].split("|")
+    rep, vis, zero, _ = line[1:].split("|")
     return [int(x) for x in rep.split()], [int(x) for x in vis.split()], zero.strip() == "1"
+
+
+def parse_stats(line):
+    """the arm counters of the last repair (update_plan::Stats), by name"""
+    return {k: int(v) for k, v in (x.split("=") for x in line[1:].split("|")[3].split())}
 
 
 class Oracle:
@@ -371,7 +376,7 @@ def scripted(program, t, rules, blen, mods, changed, oracle=True):
     lines = tree_lines(t, 0) + ["rebuild 0", rules, "blen %d %s" % (len(blen), " ".join("%s %d" % (float(x).hex(), f) for x, f in blen))]
     lines += mod_lines(mods) + ["repair %d %s" % (len(changed), " ".join(map(str, changed))), "check"]
     out = run(program, lines)
-    res = dict(result=parse_result(out[3]), state=parse_state(out[4]), log=parse_log(out[5]), book=parse_book(out[6]), same=out[7] == "same 1")
+    res = dict(result=parse_result(out[3]), state=parse_state(out[4]), log=parse_log(out[5]), book=parse_book(out[6]), stats=parse_stats(out[6]), same=out[7] == "same 1")
     assert res["book"][2], "flags left set"
     if oracle:
         orc = Oracle(t)
@@ -398,11 +403,15 @@ def test_none_in_the_lower_pass(program, name):
     assert r["state"][4][3] == 1.5e-4 and r["state"][4][4] == 0.0
     assert r["log"][1][:3] == ["I", "E", "I"] and r["log"][0][:2] == [[(1, 3)], [(1, 3)]] and r["log"][1].count("E") == 1
     assert {3, 1} <= set(r["book"][0]) and {3, 1} <= set(r["book"][1])
+    st = r["stats"]
+    assert (st["rounds"], st["phaseA_none"], st["phaseA_reest_first"], st["phaseA_reest_second"]) == (1, 1, 1, 0), st
+    assert st["items_mode0"] >= 2 and st["upper_none_totup"] + st["upper_none_upright"] + st["upper_none_upleft"] == 0, st
     # it stays at zero (False): the other child is estimated too
     r = scripted(program, t, LOWER_ZERO, [(1.5e-4, 1), (2.5e-4, 0)], new3, [3])
     assert r["result"] == r["py"] and r["state"] == r["py_state"] and r["same"]
     assert r["state"][4][3] == 0.0 and r["state"][4][4] == 2.5e-4 and r["log"][1][:4] == ["I", "E", "E", "I"]
     assert {3, 4, 1} <= set(r["book"][0])
+    assert (r["stats"]["phaseA_none"], r["stats"]["phaseA_reest_first"], r["stats"]["phaseA_reest_second"]) == (1, 1, 1), r["stats"]
     # child 4 marked changed: it goes first
     d2 = list(d)
     d2[3] = 0.0
@@ -410,6 +419,7 @@ def test_none_in_the_lower_pass(program, name):
     r = scripted(program, t2, LOWER_ZERO, [(1.5e-4, 0)], [("low", 4, 78)], [4])
     assert r["result"] == r["py"] and r["state"] == r["py_state"] and r["same"]
     assert r["state"][4][4] == 1.5e-4 and r["state"][4][3] == 0.0
+    assert (r["stats"]["phaseA_reest_first"], r["stats"]["phaseA_reest_second"]) == (1, 0), r["stats"]
     # both stay at zero: the second merge is None as well
     r = scripted(program, t, LOWER_ZERO, [(0.0, 1), (0.0, 1)], new3, [3])
     assert r["result"] == ("err", FATAL, "None vector after updateBLen at node 1") and r["py"] == ("raise", "None vector after updateBLen")
@@ -446,12 +456,16 @@ def test_none_in_the_upper_pass(program, name):
         # of 2 and 4 (7)
         assert r["result"] == ("ok", 12)
     assert {1, 0} <= set(r["book"][1]) and 1 in r["book"][0]
+    st = r["stats"]
+    assert st["rounds"] == 2 and st["upper_none_upleft"] >= 1 and (st["upper_reest_node"], st["upper_reest_child"]) == (1, 0), st
+    assert st["phaseA_none"] == 0 and st["items_mode2"] >= 2 and st["items_mode1"] >= 1, st
     # it stays at zero: the branch of the child that was being merged is estimated, and that child starts the next round
     r = scripted(program, t, UPPER_ZERO, [(0.0, 1), (2.5e-4, 0)], both, [3, 4], oracle=False)
     assert r["result"][0] == "ok" and r["same"]
     assert r["state"][4][1] == 0.0 and r["state"][4][3] == 2.5e-4 and r["log"][1].count("E") == 2
     assert r["state"][3][1] is None and r["state"][3][3] is not None                 # probVectTotUp: none at 1, one at 3 now
     assert {1, 0, 3} <= set(r["book"][1]) and {1, 3} <= set(r["book"][0])
+    assert r["stats"]["rounds"] == 2 and (r["stats"]["upper_reest_node"], r["stats"]["upper_reest_child"]) == (1, 1), r["stats"]
     # neither can be lengthened
     r = scripted(program, t, UPPER_ZERO, [(0.0, 1), (0.0, 1)], both, [3, 4], oracle=False)
     assert r["result"] == ("err", FATAL, "None upper vector at node 1 and no branch length to lengthen")
@@ -465,10 +479,12 @@ def test_none_in_the_upper_pass(program, name):
     t3 = make_case(name, False, d3)
     r = scripted(program, t3, TOTUP_ANY, [(0.0, 1)], [("low", 3, 77)], [3], oracle=False)
     assert r["result"] == ("err", FATAL, "None upper vector at node 1 and no branch length to lengthen") and r["log"][1].count("E") == 1
+    assert r["stats"]["upper_none_totup"] == 1 and (r["stats"]["upper_reest_node"], r["stats"]["upper_reest_child"]) == (1, 0), r["stats"]
     # ... and a script that keeps answering None, whatever the new length: the cap on the rounds
     r = scripted(program, t3, TOTUP_ANY, [(1e-4 + 1e-7 * i, 0) for i in range(2000)], [("low", 3, 77)], [3], oracle=False)
     assert r["result"] == ("err", FATAL, "updatePartials keeps finding inconsistent zero-length branches")
     assert r["log"][1].count("E") >= 64
+    assert r["stats"]["rounds"] == 64 and r["stats"]["upper_none_totup"] >= 64, r["stats"]
     assert sum((0, 3) in c for c in r["log"][0]) == 64                                # one lower list of the root per round
 
 

@@ -217,7 +217,11 @@ int main()
             bool zero = scratch.touched.empty();
             for (const std::vector<uint8_t> *f : {&scratch.dLow, &scratch.dUp, &scratch.dDist, &scratch.dCh0, &scratch.dCh1, &scratch.inFrontier, &scratch.inTodo})
                 for (uint8_t x : *f) zero = zero && !x;
-            printf(" | %d\n", zero ? 1 : 0);
+            printf(" | %d |", zero ? 1 : 0);
+#define PRINT_STAT(name) printf(" " #name "=%lld", (long long)scratch.stats.name);
+            UPDATE_PLAN_STATS(PRINT_STAT)
+#undef PRINT_STAT
+            printf("\n");
         } else if (cmd == "check") {
             State again = cur;
             for (size_t v = 0; v < (size_t)cur.n; v++) if (cur.c0[v] >= 0) again.lower[v] = -1;
