@@ -126,6 +126,20 @@ int commit_known(maple_ctx *c, int32_t n, const int64_t *d_woff, const int64_t *
 // lists committed on the library's stream are not yet visible to work on another stream: wait once
 __attribute__((visibility("hidden")))
 int settle(maple_ctx *c);
+static int need_tree_and_model(maple_ctx *c)
+{
+    if (!c->tree_set) return fail(c, MAPLE_ERR_STATE, "maple_tree_upload has not been called");
+    return need_model(c);
+}
+// what every call over the uploaded tree begins with (a call with refusals of its own that touch nothing checks
+// need_tree_and_model, refuses, and then begins)
+static int begin_tree_call(maple_ctx *c)
+{
+    TRY(need_tree_and_model(c));
+    HIPCK(c, hipSetDevice(c->device));
+    ahead_quiesce(c);                                                    // (the rows made ahead stay as they are)
+    return settle(c);
+}
 // evaluatePlacement for n items (maple_evaluate_placement_batch; comp2 optional, 2 doubles per item: see k_evalplace)
 __attribute__((visibility("hidden")))
 int evaluate_placement_items(maple_ctx *c, int32_t n, const int32_t *midTot, const int32_t *down, const int32_t *up, const double *dist,

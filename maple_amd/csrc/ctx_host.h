@@ -234,6 +234,7 @@ struct maple_ctx {
     maple_params params{};
     int32_t lRef = 0;
     std::vector<uint8_t> refIdx;
+    DevBuf<uint8_t> d_refIdx;          // the same on the device, uploaded on first use (device_ref_idx, branch_walk_host.h)
     DevModel dm{};                     // device pointers inside
     DevBuf<DevModel> d_model;          // the same struct in device memory: what the kernels read
     bool model_set = false;

@@ -18,7 +18,7 @@
 // reference frame (M:10107-10109, then passMutationListThroughBranch, M:10027, down the path): derived here once per uploaded
 // tree, one list per reference node in CSR; a node's frame is its nearest ancestor-or-self with mutations.
 // Maximisation (M:10852-10947): em_mstep.h on the host.
-#include "batch_host.h"
+#include "branch_walk_host.h"
 #include "em_mstep.h"
 
 #include <utility>
@@ -38,10 +38,9 @@ struct EmOut {
 struct EmScratch : ScratchBase {
     // frames of the uploaded tree (valid while maple_ctx::em_frames_valid)
     std::vector<int32_t> slotOfNode;   // per node at upload: CSR slot of a reference node's list, -1 otherwise
-    int32_t nSlots = 0;
+    branch_walk_plan::Rows rows;       // per call (kept for its memory)
     DevBuf<int2> d_fm;
     DevBuf<int32_t> d_fmOff;
-    DevBuf<uint8_t> d_refIdx;
     // per call
     DevBuf<int32_t> d_pl, d_cl, d_leafMinor, d_frame;
     DevBuf<double> d_dist, d_tables, d_partials;
@@ -172,11 +171,6 @@ int derive_frames(maple_ctx *c, EmScratch &S)
 {
     const int32_t n = (int32_t)c->h_tree_up.size(), root = c->dtree.root;
     S.slotOfNode.assign((size_t)n, -1);
-    S.nSlots = 0;
-    if (!S.d_refIdx.p) {
-        HIPCK(c, S.d_refIdx.reserve_exact((size_t)c->lRef));
-        HIPCK(c, hipMemcpy(S.d_refIdx.p, c->refIdx.data(), (size_t)c->lRef, hipMemcpyHostToDevice));
-    }
     std::vector<int32_t> fmOff{0};
     std::vector<int2> fmAll;
     if (c->tree_has_mut) {
@@ -206,7 +200,6 @@ int derive_frames(maple_ctx *c, EmScratch &S)
             if (c->h_tree_c0[v] >= 0) { st.push_back({c->h_tree_c0[v], mine}); st.push_back({c->h_tree_c1[v], mine}); }
         }
         for (const auto &l : lists) { fmAll.insert(fmAll.end(), l.begin(), l.end()); fmOff.push_back((int32_t)fmAll.size()); }
-        S.nSlots = (int32_t)lists.size();
     }
     HIPCK(c, S.d_fmOff.reserve(fmOff.size()));
     HIPCK(c, hipMemcpy(S.d_fmOff.p, fmOff.data(), fmOff.size() * sizeof(int32_t), hipMemcpyHostToDevice));
@@ -223,57 +216,27 @@ struct EmHost {                        // the statistics on the host, as they st
 
 int expectation(maple_ctx *c, const int32_t *nMinorArr, EmHost &H)
 {
-    if (!c->tree_set) return fail(c, MAPLE_ERR_STATE, "maple_tree_upload has not been called");
-    TRY(need_model(c));
-    HIPCK(c, hipSetDevice(c->device));
-    ahead_quiesce(c);                                                    // (the rows made ahead stay as they are)
-    TRY(settle(c));
+    TRY(begin_tree_call(c));
     EmScratch &S = scratch(c);
-    if (!c->em_frames_valid) TRY(derive_frames(c, S));
+    const int32_t n = (int32_t)c->h_tree_up.size(), lRef = c->lRef;
     const bool RV = c->dm.useRateVariation, U = c->dm.usingErrorRate, SS = c->dm.errorRateSiteSpecific;
-    const int32_t n = (int32_t)c->h_tree_up.size(), root = c->dtree.root, lRef = c->lRef;
-    const int32_t nl = (int32_t)c->h_n_ent.size();
-    // the branches to walk, depth-first from the root, each with the frame it lives in
-    std::vector<int32_t> node, pl, cl, leafMinor, frame, passIdx, passList, passMut;
-    std::vector<double> dist;
-    int64_t numTips = 0;
-    {
-        std::vector<std::pair<int32_t, int32_t>> st{{root, -1}};
-        while (!st.empty()) {
-            const auto [v, above] = st.back();
-            st.pop_back();
-            int32_t mine = above;
-            if (c->h_tree_mut[v] >= 0) {
-                if (v >= (int32_t)S.slotOfNode.size() || S.slotOfNode[v] < 0) return fail(c, MAPLE_ERR_STATE, "node %d has mutations the uploaded tree did not have", v);
-                mine = S.slotOfNode[v];
-            }
-            const bool leaf = c->h_tree_c0[v] < 0;
-            const int32_t nm = nMinorArr ? nMinorArr[v] : 0;
-            if (nm < 0) return fail(c, MAPLE_ERR_ARG, "nMinor[%d] = %d", v, nm);
-            if (leaf) numTips += 1 + nm;                                 // M:10140-10142
-            const int32_t p = c->h_tree_up[v];
-            const double d = c->h_tree_dist[v];
-            if (p >= 0 && (d != 0.0 || (U && leaf))) {                   // M:10146
-                const int32_t pList = (c->h_tree_c0[p] == v) ? c->h_tree_upRight[p] : c->h_tree_upLeft[p];   // M:10150-10153
-                const int32_t cList = c->h_tree_lower[v];
-                if (pList < 0 || pList >= nl || cList < 0 || cList >= nl)
-                    return fail(c, MAPLE_ERR_STATE, "node %d: the branch above it has no upper list of its parent or no lower list", v);
-                if (c->h_tree_mut[v] >= 0) { passIdx.push_back((int32_t)node.size()); passList.push_back(pList); passMut.push_back(c->h_tree_mut[v]); }
-                node.push_back(v); pl.push_back(pList); cl.push_back(cList); dist.push_back(d);
-                leafMinor.push_back(leaf ? nm : -1); frame.push_back(mine);
-            }
-            if (!leaf) { st.push_back({c->h_tree_c0[v], mine}); st.push_back({c->h_tree_c1[v], mine}); }
-        }
+    branch_walk_plan::Rows &rows = S.rows;
+    TRY(gather_branches(c, branch_walk_plan::EM, nMinorArr, rows));     // (refuses columns that are no tree: the frames below trust them)
+    if (!c->em_frames_valid) TRY(derive_frames(c, S));
+    const int32_t nB = rows.size();
+    std::vector<int32_t> frame((size_t)nB, -1);                          // the frame each branch lives in, in the tree as it stands
+    for (int32_t k = 0; k < nB; k++) {
+        const int32_t ref = rows.refNode[k];
+        if (ref < 0) continue;
+        if (ref >= (int32_t)S.slotOfNode.size() || S.slotOfNode[ref] < 0)
+            return fail(c, MAPLE_ERR_STATE, "node %d has mutations the uploaded tree did not have", ref);
+        frame[k] = S.slotOfNode[ref];
     }
-    const int32_t nB = (int32_t)node.size();
+    const uint8_t *d_refIdx = nullptr;
+    TRY(device_ref_idx(c, &d_refIdx));
     MarkGuard guard{c};                // the call's temporaries (the parent lists passed through reference branches) go on every path
     TRY(guard.take());
-    if (!passIdx.empty()) {                                              // M:10154-10155, all reference branches in one launch
-        std::vector<uint8_t> down(passIdx.size(), 0);
-        std::vector<int32_t> out(passIdx.size());
-        TRY(maple_pass_branch_batch(c, (int32_t)passIdx.size(), passList.data(), passMut.data(), down.data(), out.data()));
-        for (size_t k = 0; k < passIdx.size(); k++) pl[passIdx[k]] = out[k];
-    }
+    TRY(pass_parent_lists(c, rows, false));
     const size_t L1 = (size_t)lRef + 1;
     const size_t nTab = 4 * L1 + 3 * L1;                                 // wts, cs, tn, ecs: 7 x (lRef + 1) doubles
     const int blocks = std::max(1, (nB + EM_BLOCK - 1) / EM_BLOCK);
@@ -284,18 +247,18 @@ int expectation(maple_ctx *c, const int32_t *nMinorArr, EmHost &H)
     HIPCK(c, hipMemsetAsync(S.d_tables.p, 0, nTab * sizeof(double), c->stream));
     HIPCK(c, hipMemsetAsync(S.d_obs.p, 0, (L1 + 1) * sizeof(unsigned long long), c->stream));
     HIPCK(c, hipMemsetAsync(S.d_fatal.p, 0, sizeof(int32_t), c->stream));
-    TRY(h2d(c, S.d_pl, pl.data(), (size_t)nB));
-    TRY(h2d(c, S.d_cl, cl.data(), (size_t)nB));
-    TRY(h2d(c, S.d_leafMinor, leafMinor.data(), (size_t)nB));
+    TRY(h2d(c, S.d_pl, rows.pList.data(), (size_t)nB));
+    TRY(h2d(c, S.d_cl, rows.cList.data(), (size_t)nB));
+    TRY(h2d(c, S.d_leafMinor, rows.leafMinor.data(), (size_t)nB));
     TRY(h2d(c, S.d_frame, frame.data(), (size_t)nB));
-    TRY(h2d(c, S.d_dist, dist.data(), (size_t)nB));
+    TRY(h2d(c, S.d_dist, rows.dist.data(), (size_t)nB));
     EmOut o{S.d_partials.p, S.d_tables.p, S.d_tables.p + 4 * L1, S.d_tables.p + 5 * L1, S.d_tables.p + 6 * L1, S.d_obs.p, S.d_fatal.p};
     hipEvent_t e0, e1;                 // (maple_timing_*: the walk's own time, what tools/mutation_events_stats.py compares with)
     TRY(ev_pair(c, &e0, &e1, MAPLE_K_OTHER, (double)nB, 0.0));
     HIPCK(c, hipEventRecord(e0, c->stream));
     DISPATCH3(c, k_em_walk, <<<dim3(blocks), dim3(EM_BLOCK), 0, c->stream>>>(c->d_model.p, view(c), nB, S.d_pl.p, S.d_cl.p, S.d_dist.p,
                                                                             S.d_leafMinor.p, S.d_frame.p, S.d_fm.p, S.d_fmOff.p,
-                                                                            S.d_refIdx.p, o));
+                                                                            d_refIdx, o));
     HIPCK(c, hipGetLastError());
     HIPCK(c, hipEventRecord(e1, c->stream));
     std::vector<double> partials((size_t)blocks * EM_NACC), tables(nTab);
@@ -315,7 +278,7 @@ int expectation(maple_ctx *c, const int32_t *nMinorArr, EmHost &H)
     for (int i = 0; i < 16; i++) T.counts[i] = sum[4 + i];
     T.errorCount = U ? sum[20] : 0.0;
     T.totTreeLength = RV ? sum[21] : 0.0;
-    T.numTips = numTips;
+    T.numTips = rows.numTips;
     T.observedTotNucsSites = U ? (int64_t)obs[L1] : 0;
     H.wts.assign(tables.begin(), tables.begin() + 4 * (size_t)lRef);
     H.cs.assign(tables.begin() + 4 * L1, tables.begin() + 4 * L1 + lRef);

@@ -12,7 +12,7 @@
 // A zero denominator (the reference's ZeroDivisionError) ends the lane's walk and notes (leaf, position) in one 64-bit word with an
 // integer atomicMin, so that the first leaf of the report's order is the one named; nothing traps.
 // A translation unit of libmaple_hip.so (gfx950 only).
-#include "batch_host.h"
+#include "branch_walk_host.h"
 
 #include <utility>
 
@@ -28,6 +28,7 @@ struct ErrSink {                       // where the records go; pos == nullptr: 
 };
 
 struct ErrScratch : ScratchBase {      // per call
+    branch_walk_plan::Rows rows;       // (kept for its memory)
     DevBuf<int32_t> d_pl, d_cl, d_count, d_pos;
     DevBuf<double> d_dist, d_prob;
     DevBuf<int64_t> d_off;
@@ -87,43 +88,18 @@ extern "C" int maple_tree_error_probs(maple_ctx *c, const int32_t *nMinorArr, do
                                       double *outProb, int64_t *nRecords)
 {
     if (!c || !nLeaves || !nRecords || capLeaves < 0 || cap < 0 || (capLeaves > 0 && (!leafNode || !outOff))) return MAPLE_ERR_ARG;
-    if (!c->tree_set) return fail(c, MAPLE_ERR_STATE, "maple_tree_upload has not been called");
-    TRY(need_model(c));
+    TRY(need_tree_and_model(c));
     if (!c->dm.usingErrorRate)
         return fail(c, MAPLE_ERR_STATE, "the model has no error rate (the reference reports errors only under an error model)");
     if (cap > 0 && (!outPos || !outAllele || !outProb)) return fail(c, MAPLE_ERR_ARG, "cap = %lld without the record arrays", (long long)cap);
-    HIPCK(c, hipSetDevice(c->device));
-    ahead_quiesce(c);                                                    // (the rows made ahead stay as they are)
-    TRY(settle(c));
+    TRY(begin_tree_call(c));
     ErrScratch &S = scratch(c);
-    const int32_t root = c->dtree.root;
-    const int32_t nl = (int32_t)c->h_n_ent.size(), nml = (int32_t)c->h_mut_cnt.size();
-    // the leaves in the order the reference's traversal meets them (M:9801-10020: children[v][0] before children[v][1]); the walked
-    // ones -- no minor sequences, M:9805 -- are the kernel's items
-    std::vector<int32_t> leaves, itemLeaf, pl, cl, passIdx, passList, passMut;
-    std::vector<double> dist;
-    {
-        std::vector<int32_t> st{root};
-        while (!st.empty()) {
-            const int32_t v = st.back();
-            st.pop_back();
-            const int32_t nm = nMinorArr ? nMinorArr[v] : 0;
-            if (nm < 0) return fail(c, MAPLE_ERR_ARG, "nMinor[%d] = %d", v, nm);
-            if (c->h_tree_c0[v] >= 0) { st.push_back(c->h_tree_c1[v]); st.push_back(c->h_tree_c0[v]); continue; }
-            const int32_t p = c->h_tree_up[v];
-            if (nm == 0 && p >= 0) {                                     // (a root without children: the reference fails on up[root])
-                const int32_t pList = (c->h_tree_c0[p] == v) ? c->h_tree_upRight[p] : c->h_tree_upLeft[p];   // M:9809-9812
-                const int32_t cList = c->h_tree_lower[v], mu = c->h_tree_mut[v];
-                if (pList < 0 || pList >= nl || cList < 0 || cList >= nl)
-                    return fail(c, MAPLE_ERR_STATE, "node %d: the branch above it has no upper list of its parent or no lower list", v);
-                if (mu >= nml) return fail(c, MAPLE_ERR_STATE, "node %d: mutList[] = %d is not a mutation-list id (have %d)", v, mu, nml);
-                if (mu >= 0) { passIdx.push_back((int32_t)itemLeaf.size()); passList.push_back(pList); passMut.push_back(mu); }
-                itemLeaf.push_back((int32_t)leaves.size()); pl.push_back(pList); cl.push_back(cList); dist.push_back(c->h_tree_dist[v]);
-            }
-            leaves.push_back(v);
-        }
-    }
-    const int32_t nL = (int32_t)leaves.size(), nI = (int32_t)itemLeaf.size();
+    // the leaves in the order the reference's traversal meets them (M:9801-10020); the walked ones -- no minor sequences, M:9805 --
+    // are the kernel's items
+    branch_walk_plan::Rows &rows = S.rows;
+    TRY(gather_branches(c, branch_walk_plan::ERRORS, nMinorArr, rows));
+    const std::vector<int32_t> &leaves = rows.leaves, &itemLeaf = rows.itemLeaf;
+    const int32_t nL = (int32_t)leaves.size(), nI = rows.size();
     *nLeaves = nL;
     *nRecords = 0;
     if (nL > capLeaves) return fail(c, MAPLE_ERR_ARG, "capLeaves = %d, the tree has %d leaves", capLeaves, nL);
@@ -133,29 +109,15 @@ extern "C" int maple_tree_error_probs(maple_ctx *c, const int32_t *nMinorArr, do
     TRY(guard.take());
     const int blocks = (nI + ERR_BLOCK - 1) / ERR_BLOCK;
     if (nI > 0) {
-        if (!passIdx.empty()) {                                          // M:9813-9814, all reference branches in one launch
-            std::vector<uint8_t> down(passIdx.size(), 0);
-            std::vector<int32_t> out(passIdx.size(), -1);
-            hipEvent_t p0, p1;                                           // (timed like the two walks: the pass, its commit and their waits)
-            TRY(ev_pair(c, &p0, &p1, MAPLE_K_OTHER, (double)passIdx.size(), 0.0));
-            HIPCK(c, hipEventRecord(p0, c->stream));
-            const int rcPass = maple_pass_branch_batch(c, (int32_t)passIdx.size(), passList.data(), passMut.data(), down.data(), out.data());
-            HIPCK(c, hipEventRecord(p1, c->stream));                     // (also when the pass failed: a pair is read as a pair)
-            TRY(rcPass);
-            for (size_t k = 0; k < passIdx.size(); k++) {
-                if (out[k] < 0) return fail(c, MAPLE_ERR_FATAL, "node %d: its parent's upper list could not be passed through its mutation list",
-                                            leaves[itemLeaf[passIdx[k]]]);
-                pl[passIdx[k]] = out[k];
-            }
-        }
+        TRY(pass_parent_lists(c, rows, true));
         const unsigned long long none = ~0ull;
         unsigned long long fatal = none;
         HIPCK(c, S.d_count.reserve((size_t)nI));
         HIPCK(c, S.d_fatal.reserve(1));
         HIPCK(c, hipMemcpyAsync(S.d_fatal.p, &none, sizeof none, hipMemcpyHostToDevice, c->stream));
-        TRY(h2d(c, S.d_pl, pl.data(), (size_t)nI));
-        TRY(h2d(c, S.d_cl, cl.data(), (size_t)nI));
-        TRY(h2d(c, S.d_dist, dist.data(), (size_t)nI));
+        TRY(h2d(c, S.d_pl, rows.pList.data(), (size_t)nI));
+        TRY(h2d(c, S.d_cl, rows.cList.data(), (size_t)nI));
+        TRY(h2d(c, S.d_dist, rows.dist.data(), (size_t)nI));
         hipEvent_t e0, e1;
         TRY(ev_pair(c, &e0, &e1, MAPLE_K_OTHER, (double)nI, 0.0));
         HIPCK(c, hipEventRecord(e0, c->stream));

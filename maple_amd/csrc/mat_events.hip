@@ -15,7 +15,7 @@
 //     store (maple_mut_event), an Ns record one 8-byte store (maple_n_run), each stream bounded by the item's own count.
 // Nothing is accumulated across lanes: no float atomics, no order that depends on scheduling, the same bytes on every call.
 // A translation unit of libmaple_hip.so (gfx950 only).
-#include "batch_host.h"
+#include "branch_walk_host.h"
 
 #include <utility>
 
@@ -33,12 +33,12 @@ struct MatSink {                       // where the records go; off == nullptr: 
 };
 
 struct MatScratch : ScratchBase {      // per call
+    branch_walk_plan::Rows rows;       // (kept for its memory)
     DevBuf<int32_t> d_pl, d_cl, d_leafMinor, d_count, d_fatal;
     DevBuf<double> d_dist;
     DevBuf<int64_t> d_off;
     DevBuf<uint4> d_mut, d_err;
     DevBuf<int2> d_ns;
-    DevBuf<uint8_t> d_refIdx;          // the reference, once per context (the step names the site's reference nucleotide)
 };
 
 __device__ inline uint4 event_words(int pos, int from, int to, double x)
@@ -158,82 +158,40 @@ extern "C" int maple_tree_mutation_events(maple_ctx *c, const int32_t *nMinorArr
                                           int64_t capErr, maple_mut_event *err, int64_t nRecords[3])
 {
     if (!c || !mutOff || !nsOff || !errOff || !nRecords || capMut < 0 || capNs < 0 || capErr < 0) return MAPLE_ERR_ARG;
-    if (!c->tree_set) return fail(c, MAPLE_ERR_STATE, "maple_tree_upload has not been called");
-    TRY(need_model(c));
+    TRY(need_tree_and_model(c));
     if ((capMut > 0 && !mut) || (capNs > 0 && !ns) || (capErr > 0 && !err))
         return fail(c, MAPLE_ERR_ARG, "a capacity without its record array");
-    HIPCK(c, hipSetDevice(c->device));
-    ahead_quiesce(c);                                                    // (the rows made ahead stay as they are)
-    TRY(settle(c));
+    TRY(begin_tree_call(c));
     MatScratch &S = scratch(c);
-    const bool U = c->dm.usingErrorRate;
-    const int32_t n = (int32_t)c->h_tree_up.size(), root = c->dtree.root;
-    const int32_t nl = (int32_t)c->h_n_ent.size(), nml = (int32_t)c->h_mut_cnt.size();
+    const int32_t n = (int32_t)c->h_tree_up.size();
     // the items, depth-first from the root (the order is the launch's only: the records are laid out by node id)
-    std::vector<int32_t> node, pl, cl, leafMinor, passIdx, passList, passMut;
-    std::vector<double> dist;
-    {
-        std::vector<int32_t> st{root};
-        while (!st.empty()) {
-            const int32_t v = st.back();
-            st.pop_back();
-            const bool leaf = c->h_tree_c0[v] < 0;
-            const int32_t nm = nMinorArr ? nMinorArr[v] : 0;
-            if (nm < 0) return fail(c, MAPLE_ERR_ARG, "nMinor[%d] = %d", v, nm);
-            const int32_t p = c->h_tree_up[v], cList = c->h_tree_lower[v], mu = c->h_tree_mut[v];
-            const double d = c->h_tree_dist[v];
-            if (cList < 0 || cList >= nl) return fail(c, MAPLE_ERR_STATE, "node %d has no lower list", v);
-            int32_t pList = -1;
-            if (p >= 0 && (d != 0.0 || (U && leaf))) {                   // M:10146
-                pList = (c->h_tree_c0[p] == v) ? c->h_tree_upRight[p] : c->h_tree_upLeft[p];   // M:10150-10153
-                if (pList < 0 || pList >= nl) return fail(c, MAPLE_ERR_STATE, "node %d: the branch above it has no upper list of its parent", v);
-                if (mu >= nml) return fail(c, MAPLE_ERR_STATE, "node %d: mutList[] = %d is not a mutation-list id (have %d)", v, mu, nml);
-                if (mu >= 0) { passIdx.push_back((int32_t)node.size()); passList.push_back(pList); passMut.push_back(mu); }
-            }
-            node.push_back(v); pl.push_back(pList); cl.push_back(cList); dist.push_back(d); leafMinor.push_back(leaf ? nm : -1);
-            if (!leaf) { st.push_back(c->h_tree_c1[v]); st.push_back(c->h_tree_c0[v]); }
-        }
-    }
-    const int32_t nI = (int32_t)node.size();
+    branch_walk_plan::Rows &rows = S.rows;
+    TRY(gather_branches(c, branch_walk_plan::EVENTS, nMinorArr, rows));
+    const std::vector<int32_t> &node = rows.node;
+    const int32_t nI = rows.size();
     for (int32_t v = 0; v <= n; v++) mutOff[v] = nsOff[v] = errOff[v] = 0;
     nRecords[0] = nRecords[1] = nRecords[2] = 0;
     MarkGuard guard{c};                // the call's temporaries (the parent lists passed through reference branches) go on every path
     TRY(guard.take());
-    if (!passIdx.empty()) {                                              // M:10154-10155, all reference branches in one launch
-        std::vector<uint8_t> down(passIdx.size(), 0);
-        std::vector<int32_t> out(passIdx.size(), -1);
-        hipEvent_t p0, p1;                                               // (timed like the two walks: the pass, its commit and their waits)
-        TRY(ev_pair(c, &p0, &p1, MAPLE_K_OTHER, (double)passIdx.size(), 0.0));
-        HIPCK(c, hipEventRecord(p0, c->stream));
-        const int rcPass = maple_pass_branch_batch(c, (int32_t)passIdx.size(), passList.data(), passMut.data(), down.data(), out.data());
-        HIPCK(c, hipEventRecord(p1, c->stream));                         // (also when the pass failed: a pair is read as a pair)
-        TRY(rcPass);
-        for (size_t k = 0; k < passIdx.size(); k++) {
-            if (out[k] < 0) return fail(c, MAPLE_ERR_FATAL, "node %d: its parent's upper list could not be passed through its mutation list",
-                                        node[passIdx[k]]);
-            pl[passIdx[k]] = out[k];
-        }
-    }
+    TRY(pass_parent_lists(c, rows, true));
     const int blocks = (nI + MAT_BLOCK - 1) / MAT_BLOCK;
     std::vector<int32_t> count((size_t)nI * 3, 0);
     int32_t fatal = 0;
     HIPCK(c, S.d_count.reserve((size_t)nI * 3));
-    if (!S.d_refIdx.p) {
-        HIPCK(c, S.d_refIdx.reserve_exact((size_t)c->lRef));
-        HIPCK(c, hipMemcpyAsync(S.d_refIdx.p, c->refIdx.data(), (size_t)c->lRef, hipMemcpyHostToDevice, c->stream));
-    }
+    const uint8_t *d_refIdx = nullptr;
+    TRY(device_ref_idx(c, &d_refIdx));
     HIPCK(c, S.d_fatal.reserve(1));
     HIPCK(c, hipMemsetAsync(S.d_fatal.p, 0, sizeof(int32_t), c->stream));
-    TRY(h2d(c, S.d_pl, pl.data(), (size_t)nI));
-    TRY(h2d(c, S.d_cl, cl.data(), (size_t)nI));
-    TRY(h2d(c, S.d_leafMinor, leafMinor.data(), (size_t)nI));
-    TRY(h2d(c, S.d_dist, dist.data(), (size_t)nI));
+    TRY(h2d(c, S.d_pl, rows.pList.data(), (size_t)nI));
+    TRY(h2d(c, S.d_cl, rows.cList.data(), (size_t)nI));
+    TRY(h2d(c, S.d_leafMinor, rows.leafMinor.data(), (size_t)nI));
+    TRY(h2d(c, S.d_dist, rows.dist.data(), (size_t)nI));
     {
         hipEvent_t e0, e1;
         TRY(ev_pair(c, &e0, &e1, MAPLE_K_OTHER, (double)nI, 0.0));
         HIPCK(c, hipEventRecord(e0, c->stream));
         DISPATCH3(c, k_mat_walk, <<<dim3(blocks), dim3(MAT_BLOCK), 0, c->stream>>>(c->d_model.p, view(c), nI, S.d_pl.p, S.d_cl.p, S.d_dist.p,
-                                                                                 S.d_leafMinor.p, S.d_refIdx.p, minMutProb, S.d_count.p, MatSink{},
+                                                                                 S.d_leafMinor.p, d_refIdx, minMutProb, S.d_count.p, MatSink{},
                                                                                  S.d_fatal.p));
         HIPCK(c, hipGetLastError());
         HIPCK(c, hipEventRecord(e1, c->stream));
@@ -270,7 +228,7 @@ extern "C" int maple_tree_mutation_events(maple_ctx *c, const int32_t *nMinorArr
         TRY(ev_pair(c, &e0, &e1, MAPLE_K_OTHER, (double)nI, 0.0));
         HIPCK(c, hipEventRecord(e0, c->stream));
         DISPATCH3(c, k_mat_walk, <<<dim3(blocks), dim3(MAT_BLOCK), 0, c->stream>>>(c->d_model.p, view(c), nI, S.d_pl.p, S.d_cl.p, S.d_dist.p,
-                                                                                 S.d_leafMinor.p, S.d_refIdx.p, minMutProb, S.d_count.p,
+                                                                                 S.d_leafMinor.p, d_refIdx, minMutProb, S.d_count.p,
                                                                                  MatSink{S.d_off.p, S.d_mut.p, S.d_ns.p, S.d_err.p},
                                                                                  S.d_fatal.p));
         HIPCK(c, hipGetLastError());

@@ -199,11 +199,7 @@ extern "C" int maple_tree_find_best_root(maple_ctx *c, const int32_t *nMinor, co
         return fail(c, MAPLE_ERR_ARG, "maple_tree_find_best_root: structSize is not set (sizeof(maple_root_search_params) of the caller's header)");
     maple_root_search_params P{};
     memcpy(&P, params, std::min<size_t>(params->structSize, sizeof(P)));
-    if (!c->tree_set) return fail(c, MAPLE_ERR_STATE, "maple_tree_upload has not been called");
-    TRY(need_model(c));
-    HIPCK(c, hipSetDevice(c->device));
-    ahead_quiesce(c);                                                    // (the rows made ahead stay as they are)
-    TRY(settle(c));
+    TRY(begin_tree_call(c));
     RootSearchScratch &S = scratch(c);
     if (!c->root_search_valid) TRY(build_plan(c, S));
     const int32_t n = (int32_t)c->h_tree_up.size(), root = c->dtree.root;

@@ -116,11 +116,7 @@ int build_plan(maple_ctx *c, TreeLkScratch &S)
 extern "C" int maple_tree_log_lk(maple_ctx *c, const int32_t *nMinor, double *totalLK, double *rootLK, double *nodeLK)
 {
     if (!c || !totalLK) return MAPLE_ERR_ARG;
-    if (!c->tree_set) return fail(c, MAPLE_ERR_STATE, "maple_tree_upload has not been called");
-    TRY(need_model(c));
-    HIPCK(c, hipSetDevice(c->device));
-    ahead_quiesce(c);                                                    // (the rows made ahead stay as they are)
-    TRY(settle(c));
+    TRY(begin_tree_call(c));
     TreeLkScratch &S = scratch(c);
     if (!c->tree_lk_valid) TRY(build_plan(c, S));
     const int32_t n = (int32_t)c->h_tree_up.size(), root = c->dtree.root;
