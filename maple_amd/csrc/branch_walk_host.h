@@ -1,10 +1,13 @@
 // maple_amd/csrc/branch_walk_host.h -- the host side the three calls that walk every branch of the uploaded tree share (em.hip,
 // error_probs.hip, mat_events.hip): the rows of branch_walk_plan.h from the context's columns, the parent lists of reference
-// branches passed down in one launch, and the reference nucleotides on the device.  Each entry function then reads: prologue
-// (begin_tree_call, batch_host.h), gather, pass, upload the rows, launch, scan / copy back.
+// branches passed down in one launch, the reference nucleotides on the device, the walks' block size and a launch bracketed by
+// its timing pair.  Each entry function then reads: prologue (begin_tree_call, batch_host.h), gather,
+// pass, upload the rows, launch, scan / copy back.
 #pragma once
 #include "batch_host.h"
 #include "branch_walk_plan.h"
+
+#define WALK_BLOCK 256                 // k_em_walk, k_err_walk, k_mat_walk: ONE LANE per branch, 256 branches per block
 
 static int gather_branches(maple_ctx *c, branch_walk_plan::Rule rule, const int32_t *nMinor, branch_walk_plan::Rows &rows)
 {
@@ -54,5 +57,18 @@ static int device_ref_idx(maple_ctx *c, const uint8_t **refIdx)
         HIPCK(c, e);
     }
     *refIdx = c->d_refIdx.p;
+    return MAPLE_OK;
+}
+
+// one walk launch bracketed by an event pair of its own (maple_timing_*: the kernel's time, what tools/*_stats.py report);
+// units = the items walked
+template <class Launch> static int timed_launch(maple_ctx *c, int32_t units, Launch launch)
+{
+    hipEvent_t e0, e1;
+    TRY(ev_pair(c, &e0, &e1, MAPLE_K_OTHER, (double)units, 0.0));
+    HIPCK(c, hipEventRecord(e0, c->stream));
+    launch();
+    HIPCK(c, hipGetLastError());
+    HIPCK(c, hipEventRecord(e1, c->stream));
     return MAPLE_OK;
 }

@@ -23,7 +23,6 @@
 
 #include <utility>
 
-#define EM_BLOCK 256
 #define EM_NACC 22                     // waitingTimes[4], counts[16], errorCount, totTreeLength
 
 namespace {
@@ -51,17 +50,17 @@ struct EmScratch : ScratchBase {
 __device__ inline void em_add(double *p, double x) { unsafeAtomicAdd(p, x); }
 
 template <bool RV, bool U, bool SS>
-__global__ __launch_bounds__(EM_BLOCK) void k_em_walk(const DevModel *__restrict__ mp, ArenaView av, int n, const int32_t *pl,
+__global__ __launch_bounds__(WALK_BLOCK) void k_em_walk(const DevModel *__restrict__ mp, ArenaView av, int n, const int32_t *pl,
                                                       const int32_t *cl, const double *distArr, const int32_t *leafMinor,
                                                       const int32_t *frame, const int2 *fmAll, const int32_t *fmOff,
                                                       const uint8_t *refIdx, EmOut o)
 {
     __shared__ Lds lds;
-    __shared__ double acc[EM_NACC * EM_BLOCK];
+    __shared__ double acc[EM_NACC * WALK_BLOCK];
     stage_model(*mp, lds);
     const int lane = threadIdx.x;
-    for (int k = 0; k < EM_NACC; k++) acc[k * EM_BLOCK + lane] = 0.0;
-    const int b = blockIdx.x * EM_BLOCK + lane;
+    for (int k = 0; k < EM_NACC; k++) acc[k * WALK_BLOCK + lane] = 0.0;
+    const int b = blockIdx.x * WALK_BLOCK + lane;
     if (b < n) {
         Ctx<RV, U, SS> c(*mp, lds);
         const double *rf = c.rf;
@@ -75,10 +74,10 @@ __global__ __launch_bounds__(EM_BLOCK) void k_em_walk(const DevModel *__restrict
         if (frame[b] >= 0) { fm = fmAll + fmOff[frame[b]]; nFm = fmOff[frame[b] + 1] - fmOff[frame[b]]; }
         long long obsTot = 0;
         bool fatal = false;
-        if (RV) acc[21 * EM_BLOCK + lane] = dist;                        // M:10148
-#define WT(i, x) acc[(i) * EM_BLOCK + lane] += (x)
-#define CNT(i, j, x) acc[(4 + (i) * 4 + (j)) * EM_BLOCK + lane] += (x)
-#define ERRC(x) acc[20 * EM_BLOCK + lane] += (x)
+        if (RV) acc[21 * WALK_BLOCK + lane] = dist;                        // M:10148
+#define WT(i, x) acc[(i) * WALK_BLOCK + lane] += (x)
+#define CNT(i, j, x) acc[(4 + (i) * 4 + (j)) * WALK_BLOCK + lane] += (x)
+#define ERRC(x) acc[20 * WALK_BLOCK + lane] += (x)
 #define WTS_AT(p, i, x) do { if (RV) em_add(o.wts + (size_t)(p) * 4 + (i), (x)); } while (0)
 #define WTS(i, x) WTS_AT(pos, i, x)
 #define CS(x) do { if (RV) em_add(o.cs + pos, (x)); } while (0)
@@ -124,12 +123,12 @@ __global__ __launch_bounds__(EM_BLOCK) void k_em_walk(const DevModel *__restrict
     }
     // the block's columns added in a fixed order: lane t takes lane t + stride, stride halving
     __syncthreads();
-    for (int stride = EM_BLOCK / 2; stride >= 1; stride >>= 1) {
+    for (int stride = WALK_BLOCK / 2; stride >= 1; stride >>= 1) {
         if (lane < stride)
-            for (int k = 0; k < EM_NACC; k++) acc[k * EM_BLOCK + lane] += acc[k * EM_BLOCK + lane + stride];
+            for (int k = 0; k < EM_NACC; k++) acc[k * WALK_BLOCK + lane] += acc[k * WALK_BLOCK + lane + stride];
         __syncthreads();
     }
-    if (lane < EM_NACC) o.partials[(size_t)blockIdx.x * EM_NACC + lane] = acc[lane * EM_BLOCK];
+    if (lane < EM_NACC) o.partials[(size_t)blockIdx.x * EM_NACC + lane] = acc[lane * WALK_BLOCK];
 }
 
 // passMutationListThroughBranch(list, mutations, dirIsUp=False), M:10027-10065, on (position, nucleotide) pairs
@@ -239,7 +238,7 @@ int expectation(maple_ctx *c, const int32_t *nMinorArr, EmHost &H)
     TRY(pass_parent_lists(c, rows, false));
     const size_t L1 = (size_t)lRef + 1;
     const size_t nTab = 4 * L1 + 3 * L1;                                 // wts, cs, tn, ecs: 7 x (lRef + 1) doubles
-    const int blocks = std::max(1, (nB + EM_BLOCK - 1) / EM_BLOCK);
+    const int blocks = std::max(1, (nB + WALK_BLOCK - 1) / WALK_BLOCK);
     HIPCK(c, S.d_tables.reserve(nTab));
     HIPCK(c, S.d_obs.reserve(L1 + 1));
     HIPCK(c, S.d_partials.reserve((size_t)blocks * EM_NACC));
@@ -253,14 +252,11 @@ int expectation(maple_ctx *c, const int32_t *nMinorArr, EmHost &H)
     TRY(h2d(c, S.d_frame, frame.data(), (size_t)nB));
     TRY(h2d(c, S.d_dist, rows.dist.data(), (size_t)nB));
     EmOut o{S.d_partials.p, S.d_tables.p, S.d_tables.p + 4 * L1, S.d_tables.p + 5 * L1, S.d_tables.p + 6 * L1, S.d_obs.p, S.d_fatal.p};
-    hipEvent_t e0, e1;                 // (maple_timing_*: the walk's own time, what tools/mutation_events_stats.py compares with)
-    TRY(ev_pair(c, &e0, &e1, MAPLE_K_OTHER, (double)nB, 0.0));
-    HIPCK(c, hipEventRecord(e0, c->stream));
-    DISPATCH3(c, k_em_walk, <<<dim3(blocks), dim3(EM_BLOCK), 0, c->stream>>>(c->d_model.p, view(c), nB, S.d_pl.p, S.d_cl.p, S.d_dist.p,
-                                                                            S.d_leafMinor.p, S.d_frame.p, S.d_fm.p, S.d_fmOff.p,
-                                                                            d_refIdx, o));
-    HIPCK(c, hipGetLastError());
-    HIPCK(c, hipEventRecord(e1, c->stream));
+    TRY(timed_launch(c, nB, [&] {
+        DISPATCH3(c, k_em_walk, <<<dim3(blocks), dim3(WALK_BLOCK), 0, c->stream>>>(c->d_model.p, view(c), nB, S.d_pl.p, S.d_cl.p, S.d_dist.p,
+                                                                                  S.d_leafMinor.p, S.d_frame.p, S.d_fm.p, S.d_fmOff.p,
+                                                                                  d_refIdx, o));
+    }));
     std::vector<double> partials((size_t)blocks * EM_NACC), tables(nTab);
     std::vector<unsigned long long> obs(L1 + 1);
     int32_t fatal = 0;

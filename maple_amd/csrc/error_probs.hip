@@ -16,8 +16,6 @@
 
 #include <utility>
 
-#define ERR_BLOCK 256
-
 namespace {
 
 struct ErrSink {                       // where the records go; pos == nullptr: they are only counted
@@ -39,13 +37,13 @@ struct ErrScratch : ScratchBase {      // per call
 // items = the leaves that are walked, in the report's order; count[b] = the records of item b (written when the sink only counts,
 // the bound of what is written when it stores)
 template <bool RV, bool U, bool SS>
-__global__ __launch_bounds__(ERR_BLOCK) void k_err_walk(const DevModel *__restrict__ mp, ArenaView av, int n, const int32_t *pl,
+__global__ __launch_bounds__(WALK_BLOCK) void k_err_walk(const DevModel *__restrict__ mp, ArenaView av, int n, const int32_t *pl,
                                                         const int32_t *cl, const double *distArr, double minErrorProb, int32_t *count,
                                                         ErrSink s, unsigned long long *fatal)
 {
     __shared__ Lds lds;
     stage_model(*mp, lds);
-    const int b = blockIdx.x * ERR_BLOCK + threadIdx.x;
+    const int b = blockIdx.x * WALK_BLOCK + threadIdx.x;
     if (!U || b >= n) return;                                            // (the call refuses a model without error rates)
     Ctx<RV, U, SS> c(*mp, lds);
     const double *rf = c.rf;
@@ -107,7 +105,13 @@ extern "C" int maple_tree_error_probs(maple_ctx *c, const int32_t *nMinorArr, do
     std::vector<int32_t> count((size_t)nI, 0);
     MarkGuard guard{c};                // the call's temporaries (the parent lists passed through reference branches) go on every path
     TRY(guard.take());
-    const int blocks = (nI + ERR_BLOCK - 1) / ERR_BLOCK;
+    const int blocks = (nI + WALK_BLOCK - 1) / WALK_BLOCK;
+    const auto walk = [&](ErrSink sink) {                                // the one kernel: counting, then storing
+        return timed_launch(c, nI, [&] {
+            DISPATCH3(c, k_err_walk, <<<dim3(blocks), dim3(WALK_BLOCK), 0, c->stream>>>(c->d_model.p, view(c), nI, S.d_pl.p, S.d_cl.p,
+                                                                                       S.d_dist.p, minErrorProb, S.d_count.p, sink, S.d_fatal.p));
+        });
+    };
     if (nI > 0) {
         TRY(pass_parent_lists(c, rows, true));
         const unsigned long long none = ~0ull;
@@ -118,13 +122,7 @@ extern "C" int maple_tree_error_probs(maple_ctx *c, const int32_t *nMinorArr, do
         TRY(h2d(c, S.d_pl, rows.pList.data(), (size_t)nI));
         TRY(h2d(c, S.d_cl, rows.cList.data(), (size_t)nI));
         TRY(h2d(c, S.d_dist, rows.dist.data(), (size_t)nI));
-        hipEvent_t e0, e1;
-        TRY(ev_pair(c, &e0, &e1, MAPLE_K_OTHER, (double)nI, 0.0));
-        HIPCK(c, hipEventRecord(e0, c->stream));
-        DISPATCH3(c, k_err_walk, <<<dim3(blocks), dim3(ERR_BLOCK), 0, c->stream>>>(c->d_model.p, view(c), nI, S.d_pl.p, S.d_cl.p, S.d_dist.p,
-                                                                                 minErrorProb, S.d_count.p, ErrSink{}, S.d_fatal.p));
-        HIPCK(c, hipGetLastError());
-        HIPCK(c, hipEventRecord(e1, c->stream));
+        TRY(walk(ErrSink{}));
         HIPCK(c, hipMemcpyAsync(count.data(), S.d_count.p, (size_t)nI * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
         HIPCK(c, hipMemcpyAsync(&fatal, S.d_fatal.p, sizeof fatal, hipMemcpyDeviceToHost, c->stream));
         HIPCK(c, hipStreamSynchronize(c->stream));
@@ -151,15 +149,7 @@ extern "C" int maple_tree_error_probs(maple_ctx *c, const int32_t *nMinorArr, do
     HIPCK(c, S.d_allele.reserve((size_t)total));
     HIPCK(c, S.d_prob.reserve((size_t)total));
     TRY(h2d(c, S.d_off, itemOff.data(), (size_t)nI));
-    hipEvent_t e0, e1;
-    TRY(ev_pair(c, &e0, &e1, MAPLE_K_OTHER, (double)nI, 0.0));
-    HIPCK(c, hipEventRecord(e0, c->stream));
-    DISPATCH3(c, k_err_walk, <<<dim3(blocks), dim3(ERR_BLOCK), 0, c->stream>>>(c->d_model.p, view(c), nI, S.d_pl.p, S.d_cl.p, S.d_dist.p,
-                                                                             minErrorProb, S.d_count.p,
-                                                                             ErrSink{S.d_off.p, S.d_pos.p, S.d_allele.p, S.d_prob.p},
-                                                                             S.d_fatal.p));
-    HIPCK(c, hipGetLastError());
-    HIPCK(c, hipEventRecord(e1, c->stream));
+    TRY(walk(ErrSink{S.d_off.p, S.d_pos.p, S.d_allele.p, S.d_prob.p}));
     HIPCK(c, hipMemcpyAsync(outPos, S.d_pos.p, (size_t)total * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     HIPCK(c, hipMemcpyAsync(outAllele, S.d_allele.p, (size_t)total, hipMemcpyDeviceToHost, c->stream));
     HIPCK(c, hipMemcpyAsync(outProb, S.d_prob.p, (size_t)total * sizeof(double), hipMemcpyDeviceToHost, c->stream));

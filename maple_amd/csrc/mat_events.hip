@@ -19,8 +19,6 @@
 
 #include <utility>
 
-#define MAT_BLOCK 256
-
 static_assert(sizeof(maple_mut_event) == 16 && sizeof(maple_n_run) == 8, "the records are one 16-byte / one 8-byte store");
 
 namespace {
@@ -50,14 +48,14 @@ __device__ inline uint4 event_words(int pos, int from, int to, double x)
 // count[b * 3 + k] = the records of item b in stream k (written when the sink only counts, the bound of what is written when it
 // stores)
 template <bool RV, bool U, bool SS>
-__global__ __launch_bounds__(MAT_BLOCK) void k_mat_walk(const DevModel *__restrict__ mp, ArenaView av, int n, const int32_t *pl,
+__global__ __launch_bounds__(WALK_BLOCK) void k_mat_walk(const DevModel *__restrict__ mp, ArenaView av, int n, const int32_t *pl,
                                                         const int32_t *cl, const double *distArr, const int32_t *leafMinor,
                                                         const uint8_t *refIdx, double minMutProb, int32_t *count, MatSink s,
                                                         int32_t *fatalOut)
 {
     __shared__ Lds lds;
     stage_model(*mp, lds);
-    const int b = blockIdx.x * MAT_BLOCK + threadIdx.x;
+    const int b = blockIdx.x * WALK_BLOCK + threadIdx.x;
     if (b >= n) return;
     Ctx<RV, U, SS> c(*mp, lds);
     const double *rf = c.rf;
@@ -174,7 +172,7 @@ extern "C" int maple_tree_mutation_events(maple_ctx *c, const int32_t *nMinorArr
     MarkGuard guard{c};                // the call's temporaries (the parent lists passed through reference branches) go on every path
     TRY(guard.take());
     TRY(pass_parent_lists(c, rows, true));
-    const int blocks = (nI + MAT_BLOCK - 1) / MAT_BLOCK;
+    const int blocks = (nI + WALK_BLOCK - 1) / WALK_BLOCK;
     std::vector<int32_t> count((size_t)nI * 3, 0);
     int32_t fatal = 0;
     HIPCK(c, S.d_count.reserve((size_t)nI * 3));
@@ -186,16 +184,14 @@ extern "C" int maple_tree_mutation_events(maple_ctx *c, const int32_t *nMinorArr
     TRY(h2d(c, S.d_cl, rows.cList.data(), (size_t)nI));
     TRY(h2d(c, S.d_leafMinor, rows.leafMinor.data(), (size_t)nI));
     TRY(h2d(c, S.d_dist, rows.dist.data(), (size_t)nI));
-    {
-        hipEvent_t e0, e1;
-        TRY(ev_pair(c, &e0, &e1, MAPLE_K_OTHER, (double)nI, 0.0));
-        HIPCK(c, hipEventRecord(e0, c->stream));
-        DISPATCH3(c, k_mat_walk, <<<dim3(blocks), dim3(MAT_BLOCK), 0, c->stream>>>(c->d_model.p, view(c), nI, S.d_pl.p, S.d_cl.p, S.d_dist.p,
-                                                                                 S.d_leafMinor.p, d_refIdx, minMutProb, S.d_count.p, MatSink{},
-                                                                                 S.d_fatal.p));
-        HIPCK(c, hipGetLastError());
-        HIPCK(c, hipEventRecord(e1, c->stream));
-    }
+    const auto walk = [&](MatSink sink) {                                // the one kernel: counting, then storing
+        return timed_launch(c, nI, [&] {
+            DISPATCH3(c, k_mat_walk, <<<dim3(blocks), dim3(WALK_BLOCK), 0, c->stream>>>(c->d_model.p, view(c), nI, S.d_pl.p, S.d_cl.p, S.d_dist.p,
+                                                                                       S.d_leafMinor.p, d_refIdx, minMutProb, S.d_count.p, sink,
+                                                                                       S.d_fatal.p));
+        });
+    };
+    TRY(walk(MatSink{}));
     HIPCK(c, hipMemcpyAsync(count.data(), S.d_count.p, (size_t)nI * 3 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     HIPCK(c, hipMemcpyAsync(&fatal, S.d_fatal.p, sizeof fatal, hipMemcpyDeviceToHost, c->stream));
     HIPCK(c, hipStreamSynchronize(c->stream));
@@ -223,17 +219,7 @@ extern "C" int maple_tree_mutation_events(maple_ctx *c, const int32_t *nMinorArr
     HIPCK(c, S.d_ns.reserve((size_t)tot[1] + 1));
     HIPCK(c, S.d_err.reserve((size_t)tot[2] + 1));
     TRY(h2d(c, S.d_off, itemOff.data(), (size_t)nI * 3));
-    {
-        hipEvent_t e0, e1;
-        TRY(ev_pair(c, &e0, &e1, MAPLE_K_OTHER, (double)nI, 0.0));
-        HIPCK(c, hipEventRecord(e0, c->stream));
-        DISPATCH3(c, k_mat_walk, <<<dim3(blocks), dim3(MAT_BLOCK), 0, c->stream>>>(c->d_model.p, view(c), nI, S.d_pl.p, S.d_cl.p, S.d_dist.p,
-                                                                                 S.d_leafMinor.p, d_refIdx, minMutProb, S.d_count.p,
-                                                                                 MatSink{S.d_off.p, S.d_mut.p, S.d_ns.p, S.d_err.p},
-                                                                                 S.d_fatal.p));
-        HIPCK(c, hipGetLastError());
-        HIPCK(c, hipEventRecord(e1, c->stream));
-    }
+    TRY(walk(MatSink{S.d_off.p, S.d_mut.p, S.d_ns.p, S.d_err.p}));
     if (tot[0]) HIPCK(c, hipMemcpyAsync(mut, S.d_mut.p, (size_t)tot[0] * sizeof(maple_mut_event), hipMemcpyDeviceToHost, c->stream));
     if (tot[1]) HIPCK(c, hipMemcpyAsync(ns, S.d_ns.p, (size_t)tot[1] * sizeof(maple_n_run), hipMemcpyDeviceToHost, c->stream));
     if (tot[2]) HIPCK(c, hipMemcpyAsync(err, S.d_err.p, (size_t)tot[2] * sizeof(maple_mut_event), hipMemcpyDeviceToHost, c->stream));

@@ -3,6 +3,10 @@
 // (merge_walk, genome_dev.h) and by the wavefront-wide one (merge_step, wave_update.h), so both run the same arithmetic.
 // Expects in scope: c, CT, U, SS, e1, e2, pos, newPos, bLen1, tip1, bLen2, tip2, upDown, wantLK, o, lk, totalFactor, rf, cr,
 // cer; `return` leaves the enclosing function with mergeVectors' verdict (-1 None, -2 fatal).
+// The form of a force-inlined function (newPos, lk, totalFactor by reference, merge_walk testing a status) was compiled for
+// gfx950 and left: k_merge, k_merge_wave, k_update_items and k_update_items_wave went from 72 to 184 B/lane of scratch,
+// k_fr_updating to 136 B/lane more, k_tree_lk<false,false,false> from 128 to 146 VGPRs (4 -> 3 waves/SIMD).  DESIGN.md
+// section 14 has the same story for the EM and error-report steps, there with timings.
         if (e1.type == 5 || e2.type == 5) {
             // one side carries no information: the other side is copied with its distance extended
             const bool oneIsN = (e1.type == 5);
