@@ -98,6 +98,13 @@ int maple_debug_score_rows(maple_ctx *ctx, int32_t form, int32_t nQ, const int32
 int maple_debug_update_items(maple_ctx *ctx, int32_t n, const int32_t *l1, const double *b1, const uint8_t *t1, const int32_t *l2,
                              const double *b2, const uint8_t *t2, const uint8_t *upDown, const uint8_t *mode, const int32_t *old,
                              int32_t *outList, uint8_t *outNone, uint8_t *outDiff);
+/* One chunk's estimates of maple_tree_optimize_blens on explicit items, by the library's own host function and fused kernels
+ * (maple_amd/csrc/blen_sweep.hip: one wavefront per item up to the tuning's wavePerItemMax, default 1 024 items, one lane per item
+ * above it).  Item i: estimateBranchLengthWithDerivative(upList[i] passed downwards through mutList[i] (-1: no mutation list),
+ * lowList[i], fromTipC = tip[i]): t[i] the length, isFalse[i] = 1 where the reference returns False.  The pass goes to scratch:
+ * no list is made.  An id that is no list / no mutation list is MAPLE_ERR_ARG before anything is launched. */
+int maple_debug_sweep_estimate(maple_ctx *ctx, int32_t n, const int32_t *upList, const int32_t *mutList, const int32_t *lowList,
+                               const uint8_t *tip, double *t, uint8_t *isFalse);
 /* The arms the last maple_update_partials of this context took (maple_amd/csrc/update_plan.h, UPDATE_PLAN_STATS): *n counters, the
  * first min(*n, cap) written; maple_debug_update_partials_stat_names gives their names in the same order, each followed by a blank. */
 int maple_debug_update_partials_stats(maple_ctx *ctx, int64_t *counts, int32_t cap, int32_t *n);

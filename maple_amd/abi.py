@@ -184,6 +184,8 @@ DEBUG_SIGNATURES = {
         "const int32_t *", "const int32_t *", "int64_t", "double", "double *", "uint64_t *", "int32_t *", "int64_t *")),
     "maple_debug_update_items": ("int", ("maple_ctx *", "int32_t", "const int32_t *", "const double *", "const uint8_t *", "const int32_t *",
         "const double *", "const uint8_t *", "const uint8_t *", "const uint8_t *", "const int32_t *", "int32_t *", "uint8_t *", "uint8_t *")),
+    "maple_debug_sweep_estimate": ("int", ("maple_ctx *", "int32_t", "const int32_t *", "const int32_t *", "const int32_t *", "const uint8_t *",
+        "double *", "uint8_t *")),
     "maple_debug_update_partials_stats": ("int", ("maple_ctx *", "int64_t *", "int32_t", "int32_t *")),
     "maple_debug_update_partials_stat_names": ("const char *", ()),
     "maple_debug_update_partials_visited": ("int", ("maple_ctx *", "int32_t", "int32_t *", "int32_t *")),

@@ -167,6 +167,10 @@ const std::vector<int32_t> &update_partials_visited(maple_ctx *c);
 // the list behind maple_update_partials_touched (a caller that repairs in several calls stores the union here)
 __attribute__((visibility("hidden")))
 std::vector<int32_t> &update_partials_replaced(maple_ctx *c);
+// from now on maple_update_partials leaves the root's probVectUpRight as it is where only the root's child 1 changed (update_plan.h,
+// Scratch::keepRootRight): the sweep's repair of the root's second child; the caller switches it off again
+__attribute__((visibility("hidden")))
+void update_partials_keep_root_right(maple_ctx *c, bool keep);
 // the counters of the last maple_update_partials (update_plan::Stats, in the order of UPDATE_PLAN_STATS): writes the first
 // min(cap, their number) and returns their number
 __attribute__((visibility("hidden")))
@@ -176,6 +180,12 @@ __attribute__((visibility("hidden")))
 int update_items(maple_ctx *c, int32_t n, const int32_t *l1, const double *b1, const uint8_t *t1, const int32_t *l2, const double *b2,
                  const uint8_t *t2, const uint8_t *ud, const uint8_t *mode, const int32_t *old, int32_t *outList, uint8_t *outNone,
                  uint8_t *outDiff);
+// ---- defined in blen_sweep.hip ---------------------------------------------------------------------------------------------
+// the estimates of one chunk of the branch-length sweep (the fused kernels k_sweep_estimate / k_sweep_estimate_wave); t and isFalse
+// must hold chunk.size() elements.  sweep_plan::SweepItem: sweep_plan.h
+namespace sweep_plan { struct SweepItem; }
+__attribute__((visibility("hidden")))
+int sweep_estimate(maple_ctx *c, const std::vector<sweep_plan::SweepItem> &chunk, std::vector<double> &t, std::vector<uint8_t> &isFalse);
 // ---- defined in spr_batch.hip ----------------------------------------------------------------------------------------------
 // the device tree once more from the host copy of its columns (after maple_tree_patch left tables stale)
 __attribute__((visibility("hidden")))

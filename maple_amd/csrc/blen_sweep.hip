@@ -117,8 +117,8 @@ static SweepScratch &sweep_scratch(maple_ctx *c)
     return *static_cast<SweepScratch *>(c->sweep.get());
 }
 
-// the estimates of one chunk: one launch, one copy back
-static int sweep_estimate(maple_ctx *c, const std::vector<sweep_plan::SweepItem> &chunk, std::vector<double> &t, std::vector<uint8_t> &isFalse)
+// the estimates of one chunk: one launch, one copy back (declared in batch_host.h: maple_debug_sweep_estimate calls it too)
+int sweep_estimate(maple_ctx *c, const std::vector<sweep_plan::SweepItem> &chunk, std::vector<double> &t, std::vector<uint8_t> &isFalse)
 {
     SweepScratch &S = sweep_scratch(c);
     const int n = (int)chunk.size();
@@ -285,7 +285,11 @@ extern "C" int maple_tree_optimize_blens(maple_ctx *c, int32_t n, int32_t root, 
             // (whether or not the length moved: the reference repairs, and the repair sets `dirty`)
             handed.push_back(kid[j]);
             visited.clear();
+            // (the reference's work list is [(child, 2), (root, 0)] for BOTH children, M:8790 / 8796: after the second child's
+            // repair the root's probVectUpRight, which depends on that child's length, is the one made with its old length)
+            update_partials_keep_root_right(c, j == 1);
             const int rc = repair(kid[j], visited);
+            update_partials_keep_root_right(c, false);
             S.repairs++;
             for (int w : visited) if (w >= 0 && w < n) dirty[w] = 1;
             if (rc) return finish(rc);

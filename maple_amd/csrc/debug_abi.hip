@@ -8,6 +8,7 @@
 #include "frontier_dev.h"
 #include "witness.h"
 #include "update_plan.h"
+#include "sweep_plan.h"
 
 #include <algorithm>
 
@@ -432,6 +433,26 @@ extern "C" int maple_debug_update_items(maple_ctx *c, int32_t n, const int32_t *
         if (mode[i] > 2) return fail(c, MAPLE_ERR_ARG, "mode[%d] = %d", i, mode[i]);
     TRY(need_model(c));
     return update_items(c, n, l1, b1, t1, l2, b2, t2, upDown, mode, old, outList, outNone, outDiff);
+}
+
+// ---- the branch-length sweep's fused estimate kernels on explicit items ---------------------------------------------------------
+// sweep_estimate of blen_sweep.hip itself (the id checks, the scratch offsets, the choice of kernel by wave_item_max, the copy back).
+extern "C" int maple_debug_sweep_estimate(maple_ctx *c, int32_t n, const int32_t *upList, const int32_t *mutList, const int32_t *lowList,
+                                          const uint8_t *tip, double *t, uint8_t *isFalse)
+{
+    if (!c || n < 0 || !upList || !mutList || !lowList || !tip || !t || !isFalse) return MAPLE_ERR_ARG;
+    std::vector<sweep_plan::SweepItem> items((size_t)n);
+    for (int i = 0; i < n; i++) {
+        if (mutList[i] < -1) return fail(c, MAPLE_ERR_ARG, "mutList[%d] = %d", i, mutList[i]);
+        items[i] = sweep_plan::SweepItem{i, upList[i], mutList[i], lowList[i], (uint8_t)(tip[i] != 0)};
+    }
+    TRY(need_model(c));
+    HIPCK(c, hipSetDevice(c->device));
+    std::vector<double> tv((size_t)n, 0.0);
+    std::vector<uint8_t> fv((size_t)n, 0);
+    TRY(sweep_estimate(c, items, tv, fv));
+    for (int i = 0; i < n; i++) { t[i] = tv[i]; isFalse[i] = fv[i]; }
+    return MAPLE_OK;
 }
 
 extern "C" int maple_debug_update_partials_stats(maple_ctx *c, int64_t *counts, int32_t cap, int32_t *n)

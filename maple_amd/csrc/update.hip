@@ -222,6 +222,7 @@ extern "C" int maple_update_partials(maple_ctx *c, int32_t n, int32_t root, cons
 // visited, and the list maple_update_partials_touched reports, which the sweep replaces by the union over its repairs
 const std::vector<int32_t> &update_partials_visited(maple_ctx *c) { return update_scratch(c).visitedNodes; }
 std::vector<int32_t> &update_partials_replaced(maple_ctx *c) { return update_scratch(c).replacedNodes; }
+void update_partials_keep_root_right(maple_ctx *c, bool keep) { update_scratch(c).keepRootRight = keep; }
 // the counters of update_plan::Stats of the last maple_update_partials, in the order of UPDATE_PLAN_STATS: the first cap of them
 int update_partials_stats(maple_ctx *c, int32_t cap, int64_t *counts)
 {

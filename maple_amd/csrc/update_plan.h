@@ -169,6 +169,10 @@ struct Scratch {                                  // persistent between calls: f
                                           // phase A's frontier or phase B's todo list, the nodes whose length was re-estimated --
                                           // the ones the reference's updatePartials sets `dirty` for (M:5499-5500, 5410-5411)
     Stats stats;                          // the arms the last call took
+    bool keepRootRight = false;           // the caller's, kept across calls: the root's probVectUpRight is not made again although the
+                                          // root's child 1 changed -- the reference's sweep repairs BOTH children of the root with the
+                                          // work list [(child, 2), (root, 0)] (M:8790, 8796), which for child 1 makes the root's lower
+                                          // list again and leaves the list child 0 sees as it was (maple_tree_optimize_blens sets it)
     void fit(size_t n)
     {
         if (dLow.size() < n) {
@@ -315,6 +319,7 @@ template <class Ops> struct Repair {
         if (T.c0[r] < 0) return 0;
         for (int which = 1; which >= 0; which--) {                         // upRight merges child 1, upLeft child 0
             if (!(which == 0 ? S.dCh0[r] : S.dCh1[r])) continue;
+            if (which == 1 && S.keepRootRight) continue;
             const int k = which == 1 ? T.c1[r] : T.c0[r];
             std::vector<int32_t> one{k}, pl{T.lower[k]};
             UP_TRY(passed(T, ops, pl.data(), one.data(), 1, true));

@@ -597,6 +597,18 @@ class Device:
                                                    _ptr(old), _ptr(out), _ptr(none), _ptr(diff)))
         return out, none.astype(bool), diff.astype(bool)
 
+    def debug_sweep_estimate(self, up_lists, mut_lists, low_lists, tip):
+        """One chunk's estimates of the branch-length sweep by the library's own fused kernels (maple_debug_sweep_estimate): the upper
+        list passed downwards through the mutation list (-1: none) against the lower list.  Returns (lengths, False flags)."""
+        up_lists, mut_lists, low_lists = _i32(up_lists), _i32(mut_lists), _i32(low_lists)
+        n = len(up_lists)
+        assert len(mut_lists) == n and len(low_lists) == n
+        tp = _u8(np.broadcast_to(tip, n))
+        t = np.zeros(n)
+        f = np.zeros(n, dtype=np.uint8)
+        self._ck(self.lib.maple_debug_sweep_estimate(self.h, n, _ptr(up_lists), _ptr(mut_lists), _ptr(low_lists), _ptr(tp), _ptr(t), _ptr(f)))
+        return t, f.astype(bool)
+
     def debug_update_partials_stats(self):
         """The arms the last update_partials took (maple_debug_update_partials_stats): {counter name: count}, the names as the
         library gives them (update_plan.h, UPDATE_PLAN_STATS)."""

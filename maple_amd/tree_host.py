@@ -657,8 +657,23 @@ def optimize_branch_lengths(dev: Device, tree: HostTree, effectivelyNon0BLen, di
             update_genome_lists(dev, tree, [a])
         b2 = max(both - best, 0.0)
         if b2 != dist[b]:
+            # The reference repairs BOTH children with the work list [(child, 2), (root, 0)] (M:8790, 8796).  For the second child
+            # that makes the root's lower list again and repairs below that child, but leaves probVectUpRight[root] -- and with it
+            # every upper list below the FIRST child -- as made with the second child's old length.  The repair from the child's
+            # own side makes them again: they are put back (the lists themselves stay in the arena).
+            keep, stack = [], [a]
+            while stack:
+                v = stack.pop()
+                keep.append(v)
+                stack.extend(tree.children[v])
+            keep = np.asarray(keep)
+            saved = [col[keep].copy() for col in (tree.id_upRight, tree.id_upLeft, tree.id_totUp)]
+            root_right = tree.id_upRight[root]
             dist[b] = b2
             update_genome_lists(dev, tree, [b])
+            for col, old_ids in zip((tree.id_upRight, tree.id_upLeft, tree.id_totUp), saved):
+                col[keep] = old_ids
+            tree.id_upRight[root] = root_right
     order = []
     stack = ([*tree.children[a]] if tree.children[a] else []) + ([*tree.children[b]] if tree.children[b] else [])
     while stack:                                                       # the reference's visiting order, M:8812-8822 / 8890

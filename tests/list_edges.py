@@ -1438,3 +1438,187 @@ def verdict_stable(o, it, old, mode, rel=1e-9):
         if got != want:
             return False
     return True
+
+
+# ---- the items of the branch-length sweep's fused estimate kernels (k_sweep_estimate / k_sweep_estimate_wave, blen_sweep.hip) ----------
+# An item is (upper list, mutation list of the branch or none, lower list, fromTipC): the upper list is passed downwards through the
+# mutations into per-item scratch, then estimateBranchLengthWithDerivative runs on the two lists.
+SWEEP_SEAM = (255, 256, 257, 258, 300)                            # entries of a passed upper list around the 256 the wavefront form stages
+SWEEP_STEPS = (63, 64, 65, 129)                                   # steps of the walk around a round of 64 lanes
+_ZERO_PARTNER = {fr: to for fr, to in ZERO_RATES}
+_ZERO_PARTNER.update({to: fr for fr, to in ZERO_RATES})
+
+
+def walk_steps(a, b):
+    """the steps the estimate's walk takes over two lists: one per distinct position at which an entry of either ends"""
+    ends = set()
+    for gl in (a, b):
+        pos = 0
+        for e in gl:
+            pos = e[1] if e[0] in (4, 5) else pos + 1
+            ends.add(pos)
+    return len(ends)
+
+
+def entry_at(gl, p):
+    """(entry, first site, last site) of the entry that covers site p"""
+    pos = 0
+    for e in gl:
+        end = e[1] if e[0] in (4, 5) else pos + 1
+        if p <= end:
+            return e, pos + 1, end
+        pos = end
+
+
+def fam_sweep_items(mode, o):
+    """(lists, mutation lists, items) of a mode for the oracle o (set to that mode), in the order the ONE batch has: shuffled with a
+    fixed seed, with a block of ten mutation-carrying items of very different sizes in a row.  items: dicts with iup, imut (-1: no
+    mutation list), ilow (indices), tip, name, and where the item is built for a size want_passed / want_low / want_steps.
+    The lower list of an item with mutations is in the frame below the branch: built over the mutated reference, or (the cases taken
+    from other families) passed downwards by the oracle.
+      arms     every blen_none (zero-rate modes) and blen_tenth case and every fourth append_d1_O case: bare; with a mutation list
+               away from every single-site entry; with one mutation ON such a site (the kind of the upper list's entry there --
+               inside an R run, which it splits, on a run's first or last site, on a nucleotide, on an O vector -- is in `on`); under
+               an error model with both values of fromTipC.  `rich`: upper lists with every kind of entry, half of the mutations on
+               their own entries, half of those turning the nucleotide into the reference (standard modes).
+      exits    no term at all (False); 1 / t terms only (nA = 0, nZeros > 0).  The third early exit, minA < 0 (M:5309-5310), is out
+               of reach: every a_i is a quotient of sums of products of probabilities, lengths and off-diagonal rates, all >= 0
+               (the one subtraction, M:5140 / 5264, takes 1.33333 * errorRate < 1 of a term it has just added).
+      seam     a stored upper list of at most 256 entries whose passed form has 255, 256, 257, 258 and 300 (each mutation splits a
+               tail-less R run in three), against a short lower list; lower lists of 256 and 257 entries against a short passed
+               list; both long
+      shapes   walks of 63, 64, 65 and 129 steps; 100 a_i terms; the same nucleotide on both sides (two c1 terms in one step) at
+               steps 64 and 128, the last lanes of two rounds"""
+    ref = reference()
+    u = bool(model(mode).get("usingErrorRate"))
+    zero = mode.startswith("zeroq")
+    rng = np.random.default_rng(600 + MODES.index(mode))
+    corp = corpus(mode)
+    lists, muts, items = [], [], []
+
+    def put(gl):
+        lists.append([tuple(e) for e in gl])
+        return len(lists) - 1
+
+    def new_nuc(p, avoid=()):
+        r = int(ref[p - 1])
+        return other(rng, r, tuple(avoid) + ((_ZERO_PARTNER[r],) if zero else ()))
+
+    def mutated(ms):
+        ref2 = ref.copy()
+        for (p, fr, to) in ms:
+            assert int(ref[p - 1]) == fr
+            ref2[p - 1] = to
+        return ref2
+
+    def add(name, up, ms, low, tip, reframe=False, **extra):
+        ms = sorted(tuple(int(x) for x in m) for m in ms)
+        if ms and reframe:
+            low = o.passGenomeListThroughBranch(low, ms, False)
+        imut = -1
+        if ms:
+            muts.append(ms)
+            imut = len(muts) - 1
+        items.append(dict(name=name, iup=put(up), imut=imut, ilow=put(low), tip=bool(tip), **extra))
+
+    def away_sites(a, b, k):
+        busy = [p for p, _ in sites_of(a) + sites_of(b)]
+        free = [p for p in range(15, L_REF - 15, 11) if all(abs(p - q) > 12 for q in busy)]
+        return sorted(int(p) for p in rng.choice(free, size=k, replace=False))
+
+    # -- arms of the estimate
+    base = [(("blen_none", k), c["P"], c["C"], c["fromTipC"]) for k, c in enumerate(corp.get("blen_none", []))]
+    base += [(("blen_tenth", k), c["P"], c["C"], c["fromTipC"]) for k, c in enumerate(corp.get("blen_tenth", []))]
+    base += [(("append_d1_O", k), c["P"], c["C"], c["isTipC"]) for k, c in enumerate(corp.get("append_d1_O", [])) if k % 4 == 0]
+    for j, (name, P, Cl, tip) in enumerate(base):
+        tips = (False, True) if (u and name[0] != "blen_none") else (tip,)
+        for tp in tips:
+            add((name, "bare", tp), P, [], Cl, tp)
+            add((name, "away", tp), P, [mutation(ref, p, False, new_nuc(p)) for p in away_sites(P, Cl, 2 + j % 4)], Cl, tp, reframe=True)
+        sites = sorted({p for p, _ in sites_of(P) + sites_of(Cl)})
+        for p in sites[: 3]:
+            e, first, last = entry_at(P, p)
+            kind = {6: "O", 5: "N", 4: "R_inside" if first < p < last else "R_edge"}.get(e[0], "nuc")
+            x = e[0] if (kind == "nuc" and (j + p) % 2 and not (zero and _ZERO_PARTNER[int(ref[p - 1])] == e[0])) else new_nuc(p)
+            add((name, "on", p), P, [mutation(ref, p, False, x)], Cl, tips[-1], reframe=True, on=kind if x != e[0] else "nuc_to_R")
+            if kind == "R_inside" and e[0] == 4:
+                add((name, "on_edge", first), P, [mutation(ref, first, False, new_nuc(first))], Cl, tips[-1], reframe=True, on="R_edge")
+    if not zero:
+        for k in range(8):
+            P, Cl = rich_list(rng, ref, u, [6, 10, 25][k % 3]), rich_list(rng, ref, u, 15, d1=False)
+            own = sites_of(P)
+            ms = {}
+            for j in rng.permutation(len(own))[: 6]:
+                p, e = own[int(j)]
+                x = e[0] if (e[0] < 4 and rng.random() < 0.5) else other(rng, int(ref[p - 1]))
+                ms[p] = mutation(ref, p, False, x)
+            for p in rng.integers(1, L_REF + 1, size=[1, 30, 4][k % 3]):
+                ms.setdefault(int(p), mutation(ref, int(p), False, other(rng, int(ref[int(p) - 1]))))
+            kinds = sorted({"O" if e[0] == 6 else ("nuc_to_R" if ms[p][2] == e[0] else "nuc") for p, e in own if p in ms})
+            add(("rich", k), P, [ms[p] for p in sorted(ms)], Cl, bool(k % 2), reframe=True, on_kinds=kinds)
+    # -- early exits
+    one = Builder(ref, u).nuc(400, new_nuc(400)).done()
+    add(("exit", "no_terms"), [(4, L_REF)], [], [(4, L_REF)], False)
+    add(("exit", "zeros_only"), [(4, L_REF)], [], one, False)
+    ms = [mutation(ref, p, False, new_nuc(p)) for p in (100, 900)]
+    b = Builder(mutated(ms), u)                                    # (below the branch both sides show the old reference nucleotide)
+    for (p, fr, to) in ms:
+        b.nuc(p, fr)
+    add(("exit", "no_terms_passed"), [(4, L_REF)], ms, b.done(), False)
+    add(("exit", "zeros_only_passed"), [(4, L_REF)], ms, Builder(mutated(ms), u).nuc(400, new_nuc(400)).done(), False)
+
+    # -- the 256 seam
+    def short_low(ref2, k=3):
+        b = Builder(ref2, u)
+        for p in (1200, 1230, 1260)[:k]:
+            b.nuc(p, other(rng, int(ref2[p - 1]), (int(ref[p - 1]),) + ((_ZERO_PARTNER[int(ref2[p - 1])],) if zero else ())), d0=2e-4)
+        return b.done()
+
+    def splitting(n0, m):
+        """m mutations inside the trailing R run of sized(n0), three sites apart: the passed list has n0 + 2 m entries"""
+        return [mutation(ref, p, False, new_nuc(p)) for p in range(n0 + 10, n0 + 10 + 3 * m, 3)]
+
+    for want, n0, m in ((255, 205, 25), (256, 206, 25), (257, 207, 25), (300, 250, 25), (256, 254, 1), (258, 256, 1), (257, 1, 128)):
+        ms = splitting(n0, m)
+        upper, lower = sized(ref, u, rng, n0, 1), short_low(mutated(ms))
+        for tp in ((False, True) if u else (False,)):
+            add(("seam_upper", want, n0, tp), upper, ms, lower, tp, want_passed=want, want_low=7)
+    for n_low in (256, 257):
+        ms = [mutation(ref, p, False, new_nuc(p)) for p in (20, 40, 60)]
+        add(("seam_lower", n_low), sized(ref, u, rng, 3, 1), ms, sized(mutated(ms), u, rng, n_low, 700), False, want_passed=9, want_low=n_low)
+        add(("seam_lower_bare", n_low), sized(ref, u, rng, 3, 1), [], sized(ref, u, rng, n_low, 700), False, want_passed=3, want_low=n_low)
+    ms = splitting(250, 25)
+    add(("seam_both", 300, 257), sized(ref, u, rng, 250, 1), ms, sized(mutated(ms), u, rng, 257, 700), False, want_passed=300, want_low=257)
+    # -- wave shapes
+    for steps in SWEEP_STEPS:
+        n1 = steps // 2
+        add(("steps", steps), sized(ref, u, rng, n1, 1), [], sized(ref, u, rng, steps + 1 - n1, 700), False, want_steps=steps)
+        ms = splitting(n1 - 4, 2)                                   # the same count with a pass in front
+        add(("steps_passed", steps), sized(ref, u, rng, n1 - 4, 1), ms, sized(mutated(ms), u, rng, steps + 1 - n1, 700), False,
+            want_steps=steps, want_passed=n1)
+    b = Builder(ref, u)
+    for p in range(300, 500, 2):
+        b.nuc(p, new_nuc(p), d0=1e-4 * (1 + p % 7))
+    add(("many_ais", 100), sized(ref, u, rng, 20, 1), [], b.done(), False, want_ais=100)
+    P, Cb = Builder(ref, u), Builder(ref, u)
+    for p in range(1, 129):
+        x = new_nuc(p)
+        P.nuc(p, x)
+        if p in (64, 128):
+            Cb.nuc(p, x)
+    add(("two_c1_last_lane",), P.done(), [], Cb.done(), False, same_nuc_steps=(64, 128))
+    # -- the batch's order: shuffled, then ten mutation-carrying items in a row, the largest scratch slices next to the smallest
+    order = [int(k) for k in np.random.default_rng(7).permutation(len(items))]
+    size = lambda it: len(lists[it["iup"]]) + 2 * len(muts[it["imut"]])                        # noqa: E731
+    carrying = sorted((k for k in order if items[k]["imut"] >= 0), key=lambda k: size(items[k]))
+    block = [k for pair in zip(carrying[-5:], carrying[:5]) for k in pair]
+    rest = [k for k in order if k not in block]
+    order = rest[: len(rest) // 2] + block + rest[len(rest) // 2:]
+    return lists, muts, [items[k] for k in order]
+
+
+def sweep_item_expect(o, lists, muts, it):
+    """(passed upper list, the oracle's estimate: a length or False) of an item"""
+    up = lists[it["iup"]]
+    passed = o.passGenomeListThroughBranch(up, muts[it["imut"]], False) if it["imut"] >= 0 else up
+    return passed, o.estimateBranchLengthWithDerivative(passed, lists[it["ilow"]], it["tip"])

@@ -331,6 +331,47 @@ def test_repair_matches_the_python_loop_and_the_rebuild(program, name, part, coa
         assert stopped > 0 and reached > 0, (stopped, reached)                      # the stop rule is exercised both ways
 
 
+@pytest.mark.parametrize("name", sorted(nm for nm, tr in all_trees().items() if tr[3][tr[1]] >= 0))     # (the root has children)
+def test_keep_root_right_leaves_the_first_childs_side_alone(program, name):
+    """Scratch::keepRootRight (the sweep's repair of the root's second child, as the reference's work list [(child, 2), (root, 0)]
+    leaves it): with the root's child 1 lengthened the root's lower list and the child's own side come out as in the plain repair,
+    the root's probVectUpRight and every upper list below child 0 stay what they were; the flag does nothing for child 0; and
+    once it is switched off the same repair makes everything again (the plan's own rebuild agrees)."""
+    t = make_case(name, True)
+    root = t["root"]
+    a, b = t["c0"][root], t["c1"][root]
+    below_a, stack = set(), [a]
+    while stack:
+        v = stack.pop()
+        below_a.add(v)
+        stack += [k for k in (t["c0"][v], t["c1"][v]) if k >= 0]
+    longer = lambda v: "dist %d %s" % (v, float(t["dist"][v] + 7.7e-4).hex())              # noqa: E731
+    lines = tree_lines(t, 0) + ["rebuild 0", "save",
+                                longer(b), "repair 1 %d" % b, "check",                       # 3-6: the plain repair
+                                "reset", "keepright 1", longer(b), "repair 1 %d" % b,         # 7-10: child 1 with the flag
+                                "keepright 0", "repair 1 %d" % b, "check",                   # 11-15: the flag off again
+                                "reset", "keepright 1", longer(a), "repair 1 %d" % a, "check", "keepright 0"]   # 16-20: child 0
+    out = run(program, lines)
+    base = parse_state(out[1])
+    plain = parse_state(out[4])
+    assert parse_result(out[3])[0] == "ok" and out[7] == "same 1"
+    kept = parse_state(out[9])
+    assert parse_result(out[8])[0] == "ok"
+    assert plain[1][root] != base[1][root] and kept[1][root] == base[1][root]               # probVectUpRight of the root
+    assert kept[0][root] == plain[0][root] != base[0][root] and kept[2][root] == plain[2][root]   # its lower list, probVectUpLeft
+    for v in range(t["n"]):
+        for col in (1, 2, 3):
+            if v in below_a:
+                assert kept[col][v] == base[col][v], (v, col)
+            elif v != root:
+                assert kept[col][v] == plain[col][v], (v, col)
+        assert kept[0][v] == plain[0][v] and kept[4][v] == plain[4][v]
+    assert any(plain[col][v] != base[col][v] for v in below_a for col in (1, 2, 3))            # (the plain repair does go down there)
+    assert "root_right_made=0" in out[11] and "root_right_made=1" in out[6]
+    assert parse_state(out[13]) == plain and out[16] == "same 1"
+    assert parse_result(out[17])[0] == "ok" and out[21] == "same 1"                            # child 0: the flag changes nothing
+
+
 # ---- 3: the rebuild against the Python loop; the order of a level's items ------------------------------------------------------
 
 @pytest.mark.parametrize("with_mut", [False, True])

@@ -14,6 +14,7 @@
 //   blen k (t isFalse)*k    the next k estimates
 //   repair k v*k            repair_drive -> result line "ok replaced" or "err kind|message", state line, log line, "B ..." line:
 //                           replaced nodes | visited nodes | 1 if every flag is zero again
+//   keepright 0|1           set Scratch::keepRootRight: the root's probVectUpRight is left alone where only the root's child 1 changed
 //   check                   "same 1" if a rebuild on the current lengths gives the contents of the current state
 // state line: "S lower.. | upRight.. | upLeft.. | totUp.. | dist.." (contents, - for none); log line: "L" and per items call
 // " I node:kind.." (kind 0 totUp, 1 upRight, 2 upLeft, 3 lower), per estimate " E", per pass " P<n>", root vectors " R<n>", differ " D".
@@ -222,6 +223,10 @@ int main()
             UPDATE_PLAN_STATS(PRINT_STAT)
 #undef PRINT_STAT
             printf("\n");
+        } else if (cmd == "keepright") {                              // Scratch::keepRootRight for the repairs that follow
+            int on = 0;
+            in >> on;
+            scratch.keepRootRight = on != 0;
         } else if (cmd == "check") {
             State again = cur;
             for (size_t v = 0; v < (size_t)cur.n; v++) if (cur.c0[v] >= 0) again.lower[v] = -1;
